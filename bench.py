@@ -1,8 +1,8 @@
 """Benchmark: env-steps/s of the fused racing-env step at 65 536 envs per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 65536] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 The first form with N > 1 starts the second itself, as a child process (launch_ranks).  Under
 torch.distributed.run, --gpus must equal WORLD_SIZE, and with the nccl (RCCL) backend every rank
@@ -13,16 +13,21 @@ action processing, CTBR controller, integrator, collision, gate progress,
 reward, termination, in-lane reset, observation, log reduction) over all envs
 of a rank, with pre-generated synthetic actions already resident in HBM.
 Envs shard one shard per GPU with no data-path collective ("scaling": "weak");
-`value` = envs * world_size * K / max-over-ranks wall time.
+`value` = envs * world_size * K / max-over-ranks wall time; `ms_per_step` = that wall time / K.
 
-Also reported (same JSON line): the fused kernel's roofline (HIP events over
+A plain run does only what the headline needs: it sets up, runs the W warm-up steps, times the K steps, writes the
+last timed step's outputs if --dump-outputs is given (the arrays env.step returned: obs_policy, obs_critic,
+obs_auxiliary, reward, terminated, time_out as DIR/<name>.npy, float32, rank 0's shard; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output) and prints the JSON line.
+
+With --full also reported (same JSON line): the fused kernel's roofline (HIP events over
 graph replays, algorithmic bytes from gr_bytes_per_env_step, PMC traffic from
 profiles/pmc_traffic.json) and the CPU oracle timed on the host ("port", rank 0,
 N=1 only).  Single-GPU extras: policy-in-the-loop rates (PyTorch actor; fused
 MFMA inference in one hipGraph with the step), the step on obstacle tracks, an
 env-count sweep, config C5 (32-gate tracks), Perf/total_fps of PPO training at
 4 096 envs (C2, eager and graph-captured update) and 65 536 envs, and the depth
-camera.  Every run, multi-rank included, also reports `distributed_train`: PPO training at the rank's envs with
+camera.  Every --full run, multi-rank included, also reports `distributed_train`: PPO training at the rank's envs with
 the per-mini-batch gradient all-reduce live (BASELINE C4), world-summed Perf/total_fps, per-rank update and
 all-reduce time, and a check that the ranks' parameters stay bit-identical.
 """
@@ -95,15 +100,21 @@ def parse():
     p.add_argument("--gates", type=int, default=8)
     p.add_argument("--obstacles", type=int, default=0, help="1: the reference task's walls / orbits / ground "
                    "obstacles (add_obs, add_ground_obs); 0: gates and ground only (BASELINE config C3).  The "
-                   "default line also reports the obstacle variant under 'with_obstacles'")
+                   "--full line also reports the obstacle variant under 'with_obstacles'")
     p.add_argument("--integrator", default="dd_explicit")
     p.add_argument("--no-graph", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip policy/train/cpu legs (profiling runs)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: the step kernel's roofline and steady-state rate, the update "
+                        "collective's latency (multi-rank), and the extra legs (--legs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (observations, reward, "
+                        "terminated, time_out of rank 0's envs) as DIR/<name>.npy in float32")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip policy/train/cpu legs (profiling runs)")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--legs", default="all",
-                   help="comma-separated extra legs to run (policy, obstacles, sweep, c5, regen, dtrain, train4096, "
-                        "train65536, camera, vision, cpu) or 'all'; the headline step always runs; at WORLD_SIZE > 1 "
-                        "'all' means dtrain (the data-parallel training leg) only")
+                   help="with --full: comma-separated extra legs to run (policy, obstacles, sweep, c5, regen, dtrain, "
+                        "train4096, train65536, camera, vision, cpu) or 'all'; the headline step always runs; at "
+                        "WORLD_SIZE > 1 'all' means dtrain (the data-parallel training leg) only")
     p.add_argument("--dist-backend", default="nccl",
                    help="nccl (= RCCL, one GPU per rank); gloo only to rehearse the multi-rank path with ranks "
                         "sharing one GPU")
@@ -111,8 +122,8 @@ def parse():
 
 
 def want(a, leg: str) -> bool:
-    """Whether the extra leg `leg` runs (--legs; all by default, none with --no-extras)."""
-    return not a.no_extras and (a.legs == "all" or leg in a.legs.split(","))
+    """Whether the extra leg `leg` runs (only with --full; then --legs: all by default, none with --no-extras)."""
+    return a.full and not a.no_extras and (a.legs == "all" or leg in a.legs.split(","))
 
 
 def barrier():
@@ -148,10 +159,11 @@ def make_env(n, rank, device, gates, integrator, obstacles=True, **overrides):
     return env
 
 
-def capture_graph(env, actions, length=ACTION_RING):
+def capture_graph(env, actions, length=ACTION_RING, last=None):
     """hipGraph of `length` (<= ACTION_RING) consecutive env steps (buffer bindings and action pointers baked
     in).  The host call counter is realigned to a multiple of the ring first, so every graph starts on the
-    same bindings and replays of several graphs chain like consecutive eager calls."""
+    same bindings and replays of several graphs chain like consecutive eager calls.  last: a list that receives
+    what the graph's final env.step returned (the tensors every replay leaves that step's results in)."""
     assert 1 <= length <= ACTION_RING
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -165,25 +177,28 @@ def capture_graph(env, actions, length=ACTION_RING):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         for k in range(length):
-            env.step(actions[k])
+            out = env.step(actions[k])
+    if last is not None:
+        last[:] = out
     torch.cuda.synchronize()
     graph.replay()
     torch.cuda.synchronize()
     return graph
 
 
-def time_env_steps(env, actions, steps, use_graph):
-    """Returns (seconds for exactly `steps` env steps, launch mode, the 64-step graph or None).
+def time_env_steps(env, actions, steps, use_graph, last=None):
+    """Returns (seconds for exactly `steps` env steps, launch mode, the 64-step graph or None).  last: a list that
+    receives what the last timed env.step returned (obs dict, reward, terminated, time_out, extras).
 
     Graph mode times steps // 64 replays of a 64-step graph plus one replay of a graph of the remaining
     steps % 64 launches, so any K (the driver's K=20 included) is timed as hipGraph launches."""
     graph = rem_graph = None
     reps, rem = 0, steps
     if use_graph:
-        graph = capture_graph(env, actions)
+        graph = capture_graph(env, actions, last=last)
         reps, rem = divmod(steps, ACTION_RING)
         if rem:
-            rem_graph = capture_graph(env, actions, rem)
+            rem_graph = capture_graph(env, actions, rem, last=last)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -193,12 +208,36 @@ def time_env_steps(env, actions, steps, use_graph):
         rem_graph.replay()
     elif graph is None:
         for k in range(rem):
-            env.step(actions[k % ACTION_RING])
+            out = env.step(actions[k % ACTION_RING])
+        if last is not None and rem:
+            last[:] = out
     torch.cuda.synchronize()
     barrier()
     t1 = time.perf_counter()
     del rem_graph
     return t1 - t0, ("hipgraph" if graph is not None else "eager"), graph
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, last):
+    """--dump-outputs: what the last timed env.step returned, one float32 DIR/<name>.npy per array.  Past
+    DUMP_BYTES_MAX in all, the same fixed (seeded) sample of env rows of every array is written, with its
+    indices as env_index.npy."""
+    obs, rew, term, tout = last[:4]
+    arrays = {"obs_policy": obs["policy"], "obs_critic": obs["critic"], "obs_auxiliary": obs["auxiliary"],
+              "reward": rew, "terminated": term, "time_out": tout}
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    n = len(arrays["reward"])
+    row_bytes = sum(v.nbytes for v in arrays.values()) // n + 8  # + the row's index, if sampled
+    os.makedirs(dirname, exist_ok=True)
+    if n * row_bytes > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // row_bytes, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        np.save(os.path.join(dirname, "env_index.npy"), idx.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), np.ascontiguousarray(v))
 
 
 def repeat_median(graph, n, reps=3, length=1024):
@@ -723,28 +762,52 @@ def main():
     for k in range(a.warmup):
         env.step(actions[k % ACTION_RING])
     torch.cuda.synchronize()
-    secs, mode, graph = time_env_steps(env, actions, a.steps, not a.no_graph)
+    last = []
+    secs, mode, graph = time_env_steps(env, actions, a.steps, not a.no_graph, last)
     local_secs = secs
     secs = max_over_ranks(secs, device)
     value = n * ws * a.steps / secs
-    if graph is None:  # --no-graph: the timed region ran eager, the kernel is still timed from graph replays
-        graph = capture_graph(env, actions)
-    kt = kernel_timing(graph)
-    steady = repeat_median(graph, n)
-    del graph
-    us = kt["kernel_us"]
     ms_per_step = secs * 1e3 / a.steps
-    # a per-launch kernel time cannot exceed the wall time per step of the same graph launches; only checked
-    # for a graph-timed region on a device of its own (eager launches under a PMC profiler, or rehearsal ranks
-    # sharing one GPU, interleave other work into the event window)
-    shared = ws > torch.cuda.device_count()
-    if mode == "hipgraph" and not shared and us > ms_per_step * 1e3:
-        raise RuntimeError(f"kernel_us {us:.2f} > wall us per step {ms_per_step * 1e3:.2f}: timing is inconsistent")
-    rd, wr = env.bytes_per_env_step()
-    achieved = (rd + wr) * n / (us * 1e-6) / 1e9
-    progress(f"headline: {value:.4g} env-steps/s, kernel {us:.2f} us")
-    extra = {"steady_state_env_steps_per_s_per_gpu": steady,
-             "steady_state_note": "median of 3 timed runs of 1024 steps (16 replays of the 64-step graph), one rank"}
+    if a.dump_outputs and rank == 0:  # before anything else steps the env again
+        dump_outputs(a.dump_outputs, last)
+    del last
+    extra, roofline = {}, None
+    if a.full:
+        if graph is None:  # --no-graph: the timed region ran eager, the kernel is still timed from graph replays
+            graph = capture_graph(env, actions)
+        kt = kernel_timing(graph)
+        steady = repeat_median(graph, n)
+        us = kt["kernel_us"]
+        # a per-launch kernel time cannot exceed the wall time per step of the same graph launches; only checked
+        # for a graph-timed region on a device of its own (eager launches under a PMC profiler, or rehearsal ranks
+        # sharing one GPU, interleave other work into the event window)
+        shared = ws > torch.cuda.device_count()
+        if mode == "hipgraph" and not shared and us > ms_per_step * 1e3:
+            raise RuntimeError(f"kernel_us {us:.2f} > wall us per step {ms_per_step * 1e3:.2f}: timing is inconsistent")
+        rd, wr = env.bytes_per_env_step()
+        achieved = (rd + wr) * n / (us * 1e-6) / 1e9
+        progress(f"headline: {value:.4g} env-steps/s, kernel {us:.2f} us")
+        extra = {"steady_state_env_steps_per_s_per_gpu": steady,
+                 "steady_state_note": "median of 3 timed runs of 1024 steps (16 replays of the 64-step graph), one rank"}
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": load_traffic(n, a.gates, a.obstacles),
+                    "frac_definition": "(read + written algorithmic bytes) / kernel_us / 8 TB/s",
+                    "read_achieved": rd * n / (us * 1e-6) / 1e9,
+                    "read_frac": rd * n / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                    "read_frac_definition": "the north star's HBM-read roofline: read bytes only",
+                    "kernel": ("gr::step_kernel<false, true, 0, 1>" if a.obstacles else
+                               "gr::step_kernel<true, false, 8, 1>" if a.gates <= 8 and a.integrator == "dd_explicit"
+                               else f"gr::step_kernel<true, false, {8 if a.gates <= 8 else 0}, 0>")
+                              + " (fused step)", **kt,
+                    "algorithmic_bytes_per_launch": (rd + wr) * n,
+                    # the measured floor: a pure coalesced stream of exactly these bytes in the same launch shape
+                    # and hipGraph (tools/streambench.hip, profiles/round01_streambench.json), 65 536 envs
+                    "stream_floor_us": STREAM_FLOOR_US if n == 65536 and not a.obstacles else None,
+                    "frac_of_stream_floor": STREAM_FLOOR_US / us if n == 65536 and not a.obstacles else None,
+                    "bytes_per_env_step": {"read": rd, "written": wr}}
+    else:
+        progress(f"headline: {value:.4g} env-steps/s")
+    del graph
     if ws > 1:
         # a scaling line that proves what it ran: the backend, one record per rank (its device and PCI address, its
         # own step rate over the timed region) and the latency of the update's one collective on this group
@@ -759,7 +822,7 @@ def main():
             "world_size": ws, "backend": dist.get_backend(), "ranks": ranks,
             "distinct_devices": distinct,
             "grad_allreduce_bytes": GRAD_ALLREDUCE_NUMEL * 4,
-            "grad_allreduce_median_us": allreduce_latency_us(device),
+            "grad_allreduce_median_us": allreduce_latency_us(device) if a.full else None,
             "note": "value = world_size x envs x steps / max over ranks of the timed region; ranks[i].env_steps_per_s "
                     "is rank i's own rate"}
     if want(a, "policy"):
@@ -948,7 +1011,6 @@ def main():
     if rank == 0 and ws == 1 and want(a, "cpu"):
         cpu = cpu_baseline(a.cpu_seconds, obstacles=bool(a.obstacles))
         progress("cpu_baseline")
-    traffic = load_traffic(n, a.gates, a.obstacles)
     if rank == 0:
         line = {
             "metric": "env-steps/sec whole-node @65536 envs/GPU; 1/2/4/8-GPU scaling",
@@ -968,22 +1030,8 @@ def main():
                                    f"{' with walls/orbits/ground obstacles' if a.obstacles else ', no obstacles'}, "
                                    f"{a.integrator} integrator (BASELINE config C3/C4)",
                        "num_envs_per_gpu": n, "launch": mode, "parallelism": f"env-shard x{ws}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "frac_definition": "(read + written algorithmic bytes) / kernel_us / 8 TB/s",
-                         "read_achieved": rd * n / (us * 1e-6) / 1e9,
-                         "read_frac": rd * n / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                         "read_frac_definition": "the north star's HBM-read roofline: read bytes only",
-                         "kernel": ("gr::step_kernel<false, true, 0, 1>" if a.obstacles else
-                                    "gr::step_kernel<true, false, 8, 1>" if a.gates <= 8 and a.integrator == "dd_explicit"
-                                    else f"gr::step_kernel<true, false, {8 if a.gates <= 8 else 0}, 0>")
-                                   + " (fused step)", **kt,
-                         "algorithmic_bytes_per_launch": (rd + wr) * n,
-                         # the measured floor: a pure coalesced stream of exactly these bytes in the same launch shape
-                         # and hipGraph (tools/streambench.hip, profiles/round01_streambench.json), 65 536 envs
-                         "stream_floor_us": STREAM_FLOOR_US if n == 65536 and not a.obstacles else None,
-                         "frac_of_stream_floor": STREAM_FLOOR_US / us if n == 65536 and not a.obstacles else None,
-                         "bytes_per_env_step": {"read": rd, "written": wr}},
+            "full": a.full,
+            "roofline": roofline,
             "cpu_baseline": cpu,
             # which binary ran: the sources libgr.so was built from, against this tree's (a stale build shows false)
             "libgr": {"path": _abi_mod.LIB_PATH if not os.environ.get("GR_LIB_PATH") else os.environ["GR_LIB_PATH"],

@@ -12,7 +12,7 @@
 # Presets (a NAME alone, no seconds / command):
 #   smoke        __graft_entry__.smoke()
 #   gpu_suite    pytest -m gpu, verbose, 120 s per test
-#   bench        the default bench line (bench.json)
+#   bench        the bench line with every leg, bench.py --full (bench.json)
 #   bench_driver the driver's form, --steps 20 --warmup 5, headline only (bench_driver.json)
 #   profile      scripts/gpu_profile.sh: step-kernel trace + PMC passes (prof_TAG/)
 set -o pipefail
@@ -28,7 +28,7 @@ preset() {
   case $1 in
     smoke) echo "300 python -u -c 'import __graft_entry__ as g; g.smoke()'";;
     gpu_suite) echo "1100 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread";;
-    bench) echo "600 python -u bench.py > \$OUT/bench.json";;
+    bench) echo "600 python -u bench.py --full > \$OUT/bench.json";;
     bench_driver) echo "300 python -u bench.py --steps 20 --warmup 5 --legs none > \$OUT/bench_driver.json";;
     profile) echo "900 bash scripts/gpu_profile.sh $TAG";;
     *) echo "unknown preset $1" >&2; return 1;;

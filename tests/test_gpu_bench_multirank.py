@@ -20,7 +20,8 @@ def _free_port():
         return s.getsockname()[1]
 
 
-BENCH_ARGS = ["--gpus", "2", "--steps", "128", "--warmup", "8", "--num-envs", "8192", "--dist-backend", "gloo"]
+BENCH_ARGS = ["--gpus", "2", "--steps", "128", "--warmup", "8", "--num-envs", "8192", "--dist-backend", "gloo",
+              "--full"]  # the scaling line's allreduce latency and training leg are --full measurements
 
 
 @pytest.mark.parametrize("launch", ["torchrun", "plain"])
