@@ -80,6 +80,11 @@ DEV void st4s(T4* base, size_t idx, const T4& v) {  // state planes and istate
   st4<GR_STATE_STORE_POLICY>(base, idx, v);
 }
 
+// Pins a loaded 16-byte row in its registers at this point.  The compiler otherwise sinks an LDS read into the
+// branch that uses it (the bounds branch of a row store), and the wave then pays one exposed LDS round trip per
+// use instead of one for a batch of reads.
+DEV void pin4(float4& v) { __asm__ volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
+
 // ------------------------------------------------------------- IL math
 // Isaac Lab omni.isaac.lab.utils.math restated (see oracle/gr_oracle.c).
 DEV void quat_rotate(const float q[4], const float v[3], float o[3]) {
@@ -393,17 +398,53 @@ DEV void gate_frame(const float* g, const float v[3], float o[3]) {
 // lattice mask (17 bits) of the points inside a gate frame or under the ground, and with OBST inside
 // an obstacle looked up from the grid (the substep integrator; the explicit step hands obstacles to the
 // policy waves instead).  Replaces PhysX contact / Warp mesh_tools.py:128-233; see oracle.
-// MAXG > 0: tracks of at most MAXG gates (the launch checks max_gates), the sphere pass a fixed predicated sequence
-template <bool OBST, int MAXG = 0>
+// MAXG > 0: tracks of at most MAXG gates (the launch checks max_gates), the sphere pass a fixed sequence.
+// SPHB: cull spheres read per batch (0: one predicated read per gate)
+template <bool OBST, int MAXG = 0, int SPHB = 4>
 DEV uint32_t collision_mask(const KArgs& a, const Tab& tab, int type, int lvl, const float p[3], const float q[4],
-                            const ObstGrid& og) {
+                            const ObstGrid& og, float4* keep0 = nullptr, float4* keep1 = nullptr) {
+  // keep0 (the track record when given) / keep1: rows the caller read ahead of this call for use after it; they are
+  // pinned behind the first sphere batch, whose wait covers them (LDS reads return in order)
   const float* rec = tab.rec(type, lvl);
-  const float ground = rec[0];
-  const int ng = (int)rec[3];
+  const float ground = keep0 ? keep0->x : rec[0];
+  const int ng = (int)(keep0 ? keep0->w : rec[3]);
   const float reach = a.kc->lat_reach;  // > max |lattice offset| incl. rounding
   // ---- pass 1: bounding-sphere cull, one 16-byte read (centre, r^2) per gate ----
   uint32_t sph = 0u;
-  if constexpr (MAXG > 0) {
+  if constexpr (SPHB > 0) {
+    // SPHB reads are issued together and unconditionally, so their latencies overlap: one read per gate behind
+    // its own `g < ng` branch is one exposed LDS (or L2) round trip per gate.  Rows past the track's gate count are
+    // read through an index clamped to the table's last gate row (wave-uniform, so the addresses do not wait for
+    // ng, and in bounds for every track); `g < ng` is folded into the hit as a value select.
+    const float* g0p = tab.track_base(type, lvl);
+    const int glast = tab.G - 1;
+    auto batch = [&](int gb) {
+      float4 c4[SPHB];
+#pragma unroll
+      for (int j = 0; j < SPHB; ++j)
+        c4[j] = *reinterpret_cast<const float4*>(g0p + min(gb + j, glast) * GR_GATE_FLOATS);
+#pragma unroll
+      for (int j = 0; j < SPHB; ++j) {
+        const float dx = p[0] - c4[j].x, dy = p[1] - c4[j].y, dz = p[2] - c4[j].z;
+        const bool hit = ((dx * dx + dy * dy) + dz * dz <= c4[j].w) & (gb + j < ng);
+        sph |= hit ? 1u << (gb + j) : 0u;
+      }
+    };
+    if constexpr (MAXG > 0) {
+      static_assert(MAXG % SPHB == 0, "whole batches");
+#pragma unroll
+      for (int gb = 0; gb < MAXG; gb += SPHB) {
+        batch(gb);
+        if (gb == 0 && keep0) pin4(*keep0);
+        if (gb == 0 && keep1) pin4(*keep1);
+        // keeps the batches apart (all MAXG reads in flight at once cost registers the other kernels lack)
+        if (gb + SPHB < MAXG) __asm__ volatile("" ::: "memory");
+      }
+    } else {
+#pragma unroll 1
+      for (int gb = 0; gb < ng; gb += SPHB) batch(gb);
+    }
+  } else if constexpr (MAXG > 0) {  // SPHB 0: one predicated read per gate (the substep integrator's register budget)
 #pragma unroll
     for (int g = 0; g < MAXG; ++g) {
       if (g < ng) {
@@ -827,6 +868,17 @@ DEV void store_obs_direct(const KArgs& a, int i, const ObsRows& o, float aux) {
   a.buf.obs_aux[i] = aux;
 }
 
+// the staged rows of a wave's 64 envs as fp32: the four reads first, then the four bounds-checked stores
+DEV void store_rows_f32(float4* dst, int env0, int n, const float4* stage) {
+  const int l = threadIdx.x & 63;
+  const int e = l >> 2, q = l & 3;
+  float4 v[4];
+  for (int j = 0; j < 4; ++j) v[j] = stage[q * GR_BLOCK + 16 * j + e];
+  for (int j = 0; j < 4; ++j) pin4(v[j]);
+  for (int j = 0; j < 4; ++j)
+    if (env0 + 16 * j + e < n) st4(dst, (size_t)(env0 + 16 * j + e) * 4 + q, v[j]);
+}
+
 // The same rows written by a whole wave through an LDS transpose, so each store
 // instruction covers 1 KiB of consecutive bytes (16 envs x 64 B) instead of 64
 // scattered 16-byte pieces: the store path of a CU is the tail of the step.
@@ -835,11 +887,7 @@ DEV void store_rows_staged(float4* dst, int env0, int n, const float4 rows[4], f
   const int l = threadIdx.x & 63;
   for (int q = 0; q < 4; ++q) stage[q * GR_BLOCK + l] = rows[q];
   __asm__ volatile("" ::: "memory");  // LDS ops of a wave retire in order; keep the compiler from reordering
-  for (int j = 0; j < 4; ++j) {
-    const int env = 16 * j + (l >> 2), q = l & 3;
-    const float4 v = stage[q * GR_BLOCK + env];
-    if (env0 + env < n) st4(dst, (size_t)(env0 + env) * 4 + q, v);
-  }
+  store_rows_f32(dst, env0, n, stage);
   __asm__ volatile("" ::: "memory");
 }
 
@@ -859,18 +907,17 @@ DEV void store_rows_sink(const KArgs& a, void* dst, int env0, int n, const float
   const int l = threadIdx.x & 63;
   if (a.sink_dtype == GR_DTYPE_BF16) {
     uint4* d = reinterpret_cast<uint4*>(dst);
+    const int e = l >> 1, h = l & 1;
+    float4 v[4];  // the four reads first, as in store_rows_f32
     for (int j = 0; j < 2; ++j) {
-      const int env = 32 * j + (l >> 1), h = l & 1;
-      const uint4 w = bf16x8(stage[(2 * h) * GR_BLOCK + env], stage[(2 * h + 1) * GR_BLOCK + env]);
-      if (env0 + env < n) st4(d, (size_t)(env0 + env) * 2 + h, w);
+      v[2 * j] = stage[(2 * h) * GR_BLOCK + 32 * j + e];
+      v[2 * j + 1] = stage[(2 * h + 1) * GR_BLOCK + 32 * j + e];
     }
+    for (int j = 0; j < 4; ++j) pin4(v[j]);
+    for (int j = 0; j < 2; ++j)
+      if (env0 + 32 * j + e < n) st4(d, (size_t)(env0 + 32 * j + e) * 2 + h, bf16x8(v[2 * j], v[2 * j + 1]));
   } else {
-    float4* d = reinterpret_cast<float4*>(dst);
-    for (int j = 0; j < 4; ++j) {
-      const int env = 16 * j + (l >> 2), q = l & 3;
-      const float4 v = stage[q * GR_BLOCK + env];
-      if (env0 + env < n) st4(d, (size_t)(env0 + env) * 4 + q, v);
-    }
+    store_rows_f32(reinterpret_cast<float4*>(dst), env0, n, stage);
   }
   __asm__ volatile("" ::: "memory");
 }
@@ -1191,6 +1238,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     for (int k = 0; k < 3; ++k) Jp[k] = c.dr_plant ? e.J[k] : c.inertia[k];
     float accl[3], al[3];
     int ccount = 0;
+    float ahead_z = 0.0f, ahead_g[3] = {0.0f, 0.0f, 0.0f};
     if (LEAN != 0 || c.integrator == GR_INTEGRATOR_DD_EXPLICIT) {
       dd_explicit(m, Jp, e.k2, e.k1, tt, dt, c.gravity, e.p, e.q, e.v, e.w, accl, al);
       STAMP(3);
@@ -1201,7 +1249,19 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
       }
       commit();  // barrier 1: the table is first needed by the collision test
       STAMP(14);
-      uint32_t cm = collision_mask<false, MAXG>(a, sl.tab, e.type, e.lvl, e.p, e.q, ObstGrid{});
+      // headline kernel: the track record and the current gate's centre (the terminations' reads) are issued with
+      // the first sphere batch instead of as two more dependent LDS round trips after the collision test
+      constexpr bool AHEAD = USE_LDS && MAXG > 0 && LEAN == 1;
+      float4 trec = make_float4(0.0f, 0.0f, 0.0f, 0.0f), gcur = trec;
+      if constexpr (AHEAD) {
+        trec = *reinterpret_cast<const float4*>(sl.tab.rec(e.type, e.lvl));
+        gcur = *reinterpret_cast<const float4*>(sl.tab.gate(e.type, e.lvl, e.gate));
+      }
+      // (32-gate tracks on the LDS slice keep one read per gate: batches of 4 measured +0.13 us there)
+      constexpr int SPHB = AHEAD ? 8 : (USE_LDS && MAXG == 0) ? 0 : 4;
+      uint32_t cm = collision_mask<false, MAXG, SPHB>(a, sl.tab, e.type, e.lvl, e.p, e.q, ObstGrid{},
+                                                   AHEAD ? &trec : nullptr, AHEAD ? &gcur : nullptr);
+      if constexpr (AHEAD) { ahead_z = trec.y; ahead_g[0] = gcur.x; ahead_g[1] = gcur.y; ahead_g[2] = gcur.z; }
       STAMP(15);
       if (OBST) {
         // wait for the partner policy wave's obstacle mask (same 64 envs); it is resident and never waits on us
@@ -1230,7 +1290,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
       for (int k = 0; k < 3; ++k) fb[k] = (fb[k] - (e.k2[k] * vb[k]) * gr_fabsf(vb[k])) - e.k1[k] * vb[k];
       for (int s = 0; s < c.decimation; ++s) {
         si_substep(m, Jp, fb, tt + 1, c.sim_dt, c.gravity, e.p, e.q, e.v, e.w, accl, al);
-        int cc = __builtin_popcount(collision_mask<OBST, MAXG>(a, sl.tab, e.type, e.lvl, e.p, e.q, og));
+        int cc = __builtin_popcount(collision_mask<OBST, MAXG, 0>(a, sl.tab, e.type, e.lvl, e.p, e.q, og));
         ccount = cc > ccount ? cc : ccount;
       }
     }
@@ -1242,19 +1302,25 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     const int time_out = e.ep >= c.max_episode_length;
     const int contact = ccount > c.collision_count_threshold;
     const float* rec = sl.tab.rec(e.type, e.lvl);
-    const float zw = e.p[2] + rec[1];
+    constexpr bool AHEAD_T = USE_LDS && MAXG > 0 && LEAN == 1;
+    const float zw = e.p[2] + (AHEAD_T ? ahead_z : rec[1]);
     const int oob = (zw < c.out_of_bound[0]) | (zw > c.out_of_bound[1]);
     const int bad = (1.0f - 2.0f * (e.q[1] * e.q[1] + e.q[2] * e.q[2])) < 0.0f;
     const int c_term = c.stage == 0 ? oob : contact;
     const int terminated = (c.term_contact && c_term) | (c.term_bad_pose && bad);
     const float* g = sl.tab.gate(e.type, e.lvl, e.gate);
-    float dg[3] = {g[0] - e.p[0], g[1] - e.p[1], g[2] - e.p[2]};
+    float dg[3] = {(AHEAD_T ? ahead_g[0] : g[0]) - e.p[0], (AHEAD_T ? ahead_g[1] : g[1]) - e.p[1],
+                   (AHEAD_T ? ahead_g[2] : g[2]) - e.p[2]};
     const float dist = norm3(dg);
     const int near_gate = dist < c.gate_threshold;
     int done = terminated | time_out;
     float lc[4];
     for (int k = 0; k < 4; ++k) lc[k] = th_raw[k] * sc[k] + of[k];
     lc[0] = lc[0] / e.mc;
+    // the reward weights, fetched together ahead of barrier 2 (one scalar load, wait and branch per weight after it
+    // sat on this wave's tail)
+    float rw[7];
+    for (int k = 0; k < 7; ++k) rw[k] = a.kc->w[k];
     // hand the post-step pose over to the observation waves
     xch[X_PA * GR_BLOCK + t] = make_float4(e.p[0], e.p[1], e.p[2], near_gate ? 1.0f : 0.0f);
     xch[X_Q * GR_BLOCK + t] = make_float4(e.q[0], e.q[1], e.q[2], e.q[3]);
@@ -1262,6 +1328,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     xch[X_LAG * GR_BLOCK + t] = make_float4(e.lag[0], e.lag[1], e.lag[2], e.lag[3]);
     xch[X_LC * GR_BLOCK + t] = make_float4(lc[0], lc[1], lc[2], lc[3]);
     STAMP(5);
+    __asm__ volatile("" : "+s"(rw[0]), "+s"(rw[1]), "+s"(rw[2]), "+s"(rw[3]), "+s"(rw[4]), "+s"(rw[5]), "+s"(rw[6]));
     __syncthreads();  // barrier 2: handover
     // rewards (rewards.py:154-253), IL RewardManager: f * w * dt, declaration order
     float vb[3], gb[3];
@@ -1286,7 +1353,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     f[6] = (float)bad;
     float rew = 0.0f;
     for (int k = 0; k < 7; ++k) {
-      const float wk = a.kc->w[k];
+      const float wk = rw[k];
       if (wk == 0.0f) continue;
       float v = (f[k] * wk) * dt;
       rew = rew + v;
