@@ -1112,7 +1112,8 @@ __global__ __launch_bounds__(GR_BLOCK) void env_kernel(KArgs a, const KConst* __
 // One workgroup = 256 envs and 12 waves in three roles (wave-uniform):
 //   physics (waves 0-3):   controller, integrator, collision, termination -> handover;
 //                          then reward, state planes, step outputs, reset logs
-//   policy  (waves 4-7):   observation noise while the physics runs; then the noisy
+//   policy  (waves 4-7):   while the physics collides, the observation noise and (gate-only kernels, under the
+//                          action lag) the squash of this step's action -> handover; then the noisy
 //                          policy observation, per-env gate progress, level logs
 //   episode (waves 8-11):  the next episode's start state for every env (a reset
 //                          depends only on the episode bookkeeping, not on this
@@ -1123,7 +1124,8 @@ __global__ __launch_bounds__(GR_BLOCK) void env_kernel(KArgs a, const KConst* __
 // memory / LDS / transcendental latencies overlap.  Two workgroup barriers: the
 // LDS track slice (1), the physics handover (2).
 // (ManagerBasedDiffRLEnv.step, manager_based_diff_rl_env.py:160-267.)
-// handover rows (float4 per env), physics -> others: p + aux, q, v + done, lag, last ctbr;
+// handover rows (float4 per env), physics -> others: p + aux, q, v + done, last ctbr;
+// policy -> physics: lag, this step's squashed action (gate-only kernels under action_lag = 1; otherwise unused);
 // episode -> others: the next episode's start state (state-plane layout)
 enum { X_PA = 0, X_Q = 1, X_VD = 2, X_LAG = 3, X_LC = 4, GR_XF4 = 5, GR_XF = 4 * GR_XF4 };
 enum { R_POSQ = 0, R_QV = 1, R_VW = 2, R_W = 3, R_RST0 = 4, R_RST1 = 5, GR_RF4 = 6 };
@@ -1206,7 +1208,12 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
 
   if (role == 0) {
     // ======================= physics waves =======================
-    const float4 act = ld4(reinterpret_cast<const float4*>(actions), (size_t)ii);
+    // SQUASH_HO: under the action lag the policy waves squash this step's action and hand it over.  The obstacle
+    // kernels keep the squash here: their policy waves run the obstacle test between the barriers, and with the
+    // squash behind it they measured 0.16 us slower per launch than without the move.
+    constexpr bool SQUASH_HO = !OBST;
+    const bool lagged = c.action_lag != 0;      // wave-uniform
+    const bool handed = SQUASH_HO && lagged;
     Env e;
     load_env(a, ii, e);
     const float dt = c.step_dt;
@@ -1215,12 +1222,18 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     // DiffActionManager.process_action + one-step lag.  The lag plane holds the
     // *squashed* previous action tanh(a_{t-1}): the reference only ever uses
     // tanh() of the lagged / previous raw action, so each action is squashed once.
-    float th_cur[4], th_prev[4], th_raw[4];
-    th_cur[0] = gr_tanhf(act.x); th_cur[1] = gr_tanhf(act.y); th_cur[2] = gr_tanhf(act.z); th_cur[3] = gr_tanhf(act.w);
-    for (int k = 0; k < 4; ++k) {
-      th_prev[k] = e.azero ? 0.0f : e.lag[k];
-      th_raw[k] = c.action_lag ? e.lag[k] : th_cur[k];
-      e.lag[k] = th_cur[k];
+    // Under the lag this wave's chain up to barrier 2 runs on the lag plane alone: the policy waves, which wait for
+    // barrier 2 meanwhile, squash this step's action and hand it over in xch[X_LAG] (read after barrier 2, for the
+    // two action-rate reward terms and the new lag plane).  Without the lag the command needs it at once: squashed here.
+    // (th_raw is overwritten in the branch: with `lagged ? e.lag[k] : th_cur[k]` after it the compiler selected
+    // between the two addresses and put the whole Env in scratch, 304 B / lane)
+    float th_cur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, th_prev[4], th_raw[4];
+    const float lag0[4] = {e.lag[0], e.lag[1], e.lag[2], e.lag[3]};
+    for (int k = 0; k < 4; ++k) { th_prev[k] = e.azero ? 0.0f : lag0[k]; th_raw[k] = lag0[k]; }
+    if (!handed) {
+      const float4 act = ld4(reinterpret_cast<const float4*>(actions), (size_t)ii);
+      th_cur[0] = gr_tanhf(act.x); th_cur[1] = gr_tanhf(act.y); th_cur[2] = gr_tanhf(act.z); th_cur[3] = gr_tanhf(act.w);
+      for (int k = 0; k < 4; ++k) th_raw[k] = lagged ? lag0[k] : th_cur[k];
     }
     float sc[4], of[4], cmd[4];
     action_scale(a, e.mc, sc, of);
@@ -1325,11 +1338,18 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     xch[X_PA * GR_BLOCK + t] = make_float4(e.p[0], e.p[1], e.p[2], near_gate ? 1.0f : 0.0f);
     xch[X_Q * GR_BLOCK + t] = make_float4(e.q[0], e.q[1], e.q[2], e.q[3]);
     xch[X_VD * GR_BLOCK + t] = make_float4(e.v[0], e.v[1], e.v[2], done ? 1.0f : 0.0f);
-    xch[X_LAG * GR_BLOCK + t] = make_float4(e.lag[0], e.lag[1], e.lag[2], e.lag[3]);
     xch[X_LC * GR_BLOCK + t] = make_float4(lc[0], lc[1], lc[2], lc[3]);
     STAMP(5);
     __asm__ volatile("" : "+s"(rw[0]), "+s"(rw[1]), "+s"(rw[2]), "+s"(rw[3]), "+s"(rw[4]), "+s"(rw[5]), "+s"(rw[6]));
     __syncthreads();  // barrier 2: handover
+    if constexpr (SQUASH_HO) {
+      // this step's squashed action, from the policy wave of the same 64 envs (a value select, as in
+      // merge_handover: without the lag the row is unwritten and its read unused)
+      const float4 l4 = xch[X_LAG * GR_BLOCK + t];
+      th_cur[0] = handed ? l4.x : th_cur[0]; th_cur[1] = handed ? l4.y : th_cur[1];
+      th_cur[2] = handed ? l4.z : th_cur[2]; th_cur[3] = handed ? l4.w : th_cur[3];
+    }
+    for (int k = 0; k < 4; ++k) e.lag[k] = th_cur[k];
     // rewards (rewards.py:154-253), IL RewardManager: f * w * dt, declaration order
     float vb[3], gb[3];
     quat_rotate_inverse(e.q, e.v, vb);
@@ -1416,6 +1436,18 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     e.ep = is.x; e.acc = is.y; e.epoch = is.z;
     e.gate = is.w & 0xff; e.lvl = (is.w >> 8) & 0xff; e.type = (is.w >> 24) & 0xff;
     e.nl = r0.y;
+    // Under the action lag the physics chain needs this step's squashed action only after barrier 2, and these
+    // waves wait for barrier 2 while the physics waves collide: they squash it there (the same gr_tanhf on the same
+    // lane's action) and hand it over in xch[X_LAG], a row nobody reads before barrier 2.  (Squashed before barrier
+    // 1 it made these waves the last to arrive there, behind the action's load: +0.1 us per launch.  The obstacle
+    // kernels keep the squash in the physics waves: see there.)
+    const bool lagged = !OBST && c.action_lag != 0;  // wave-uniform
+    float4 act = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (lagged) act = ld4(reinterpret_cast<const float4*>(actions), (size_t)ii);
+    auto squash_action = [&]() {
+      if (lagged)
+        xch[X_LAG * GR_BLOCK + t] = make_float4(gr_tanhf(act.x), gr_tanhf(act.y), gr_tanhf(act.z), gr_tanhf(act.w));
+    };
     ObsNoise on;
     float4 hint = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     ObstGrid og{};
@@ -1448,9 +1480,11 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
       STAMP(12);
       obs_noise(a, gid, cnt, on);  // off the critical path: needed after barrier 2
     } else {
+      STAMP(15);
       commit();  // barrier 1 (joined at once: the physics and episode waves set its time)
       STAMP(1);
-      // observation noise needs only the call counter: it runs while the physics waves collide
+      // the squash and the observation noise (which needs only the call counter) run while the physics waves collide
+      squash_action();
       obs_noise(a, gid, cnt, on);
       STAMP(2);
     }

@@ -9,6 +9,7 @@ Stamps of the step kernel (lane 0 of each wave, s_memtime shader cycles; 9/10 s_
                      5 reward + handover written, 8 after barrier 2, stores and log rows
   observation waves: 0 entry, 1 loads + obs noise, 2 table barrier, 6 reset draws,
                      7 barrier 2 + resets + gate progress, 8 observations + log rows
+  policy waves, gate-only tracks: 15 arrival at the table barrier
 """
 import json
 import os
@@ -43,7 +44,8 @@ ROLE_PHASES = {
 
 
 def run(n=int(os.environ.get("N", "65536")), steps=200):
-    os.environ["GR_LIB_PATH"] = os.path.join(OUT, "libgr.so")
+    # GR_STAMPS_LIB: another -DGR_STAMPS build (scripts/build_patched.py NAME PATCH.json -DGR_STAMPS), e.g. a parent's
+    os.environ["GR_LIB_PATH"] = os.environ.get("GR_STAMPS_LIB") or os.path.join(OUT, "libgr.so")
     import ctypes as C
 
     import numpy as np
@@ -92,6 +94,25 @@ def run(n=int(os.environ.get("N", "65536")), steps=200):
                for ph, a_, b_ in ROLE_PHASES[name]}
         for r, name in enumerate(("physics", "policy", "episode"))}
     out["slow_workgroup_ids"] = [int(b) for b in np.nonzero(wg_dur > np.percentile(wg_dur, 90))[0]]
+    # who sets barrier 1: each role's arrival at it (the stamp before its commit()) and the physics waves' release
+    # from it, in cycles after the workgroup's first wave entered (one s_memtime counter per workgroup's CU)
+    wg_t0 = np.repeat(st[:, 0].reshape(-1, 12).min(axis=1), 12)
+    arrive = {"physics": 3, "policy": 1 if obst else 15, "episode": 1}
+    b1 = {}
+    for r, name in enumerate(("physics", "policy", "episode")):
+        sel = role == r
+        if not (st[sel][:, arrive[name]] != 0).all():  # (a build without that stamp)
+            b1[name] = None
+            continue
+        d = st[sel][:, arrive[name]] - wg_t0[sel]
+        b1[name] = [float(np.percentile(d, q)) for q in (10, 50, 90)]
+    last = np.stack([st[role == r][:, arrive[name]].reshape(-1, 4).max(axis=1) for r, name in
+                     enumerate(("physics", "policy", "episode")) if b1[name] is not None], axis=1)
+    names = [nm for nm in ("physics", "policy", "episode") if b1[nm] is not None]
+    b1["last_to_arrive_share"] = {nm: float((last.argmax(axis=1) == j).mean()) for j, nm in enumerate(names)}
+    rel = st[role == 0][:, 14] - wg_t0[role == 0]
+    b1["physics_released"] = [float(np.percentile(rel, q)) for q in (10, 50, 90)]
+    out["barrier1_cycles_after_workgroup_entry p10/p50/p90"] = b1
     for r, name in enumerate(("physics", "policy", "episode")):
         sel = st[role == r]
         life = sel[:, 8] - sel[:, 0]
