@@ -210,6 +210,53 @@ class GrPolicyArgs(C.Structure):
                 ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("precision", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GrMlpNet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "w3", "b3", "h1", "z2", "y", "gy", "gz2",
+                                          "grads")] + [("ldx", C.c_int64), ("d", C.c_int32), ("k", C.c_int32),
+                                                       ("h1mask", C.c_void_p)]
+
+
+class GrMlpArgs(C.Structure):
+    _fields_ = [("net", GrMlpNet * 2), ("rows", C.c_int64), ("nets", C.c_int32), ("hidden", C.c_int32),
+                ("slope", C.c_float), ("reserved", C.c_int32), ("partial", C.c_void_p)]
+
+
+class GrPpoLossArgs(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("k", C.c_int32), ("clipped_value", C.c_int32), ("clip", C.c_float)] + [
+        (n, C.c_void_p) for n in ("mu", "std", "value", "act", "logp_old", "adv", "value_old", "ret", "mu_old",
+                                  "sig_old")] + [
+        (n, C.c_int64) for n in ("ld_mu", "ld_value", "ld_act", "ld_logp_old", "ld_adv", "ld_value_old", "ld_ret",
+                                 "ld_mu_old", "ld_sig_old")]
+
+
+class GrAdamSegment(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("step_slot", C.c_int32), ("block_start", C.c_int32)]
+
+
+class GrAdamArgs(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("nblocks", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_float), ("pad", C.c_int32), ("lr_ptr", C.c_void_p),
+                ("step", C.c_void_p), ("coef", C.c_void_p), ("part", C.c_void_p), ("seg", C.c_void_p)]
+
+
+class GrTransitionArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("k", C.c_int32), ("dones_bytes", C.c_int32), ("gamma", C.c_float),
+                ("pad", C.c_int32)] + [
+        (f, C.c_void_p) for f in ("reward", "dones", "time_out", "value", "action", "logp", "mu", "sigma")] + [
+        (f, C.c_int64) for f in ("ld_value", "ld_action", "ld_logp", "ld_mu", "ld_sigma")] + [
+        (f, C.c_void_p) for f in ("out_reward", "out_dones", "out_action", "out_value", "out_logp", "out_mu",
+                                  "out_sigma")]
+
+
+# the mirror of each struct of include/gr.h (tests/test_abi.py checks every size and field offset against the header)
+STRUCTS = {"gr_config": GrConfig, "gr_buffers": GrBuffers, "gr_camera_config": GrCameraConfig,
+           "gr_camera_buffers": GrCameraBuffers, "gr_obstacles": GrObstacles, "gr_policy_net": GrPolicyNet,
+           "gr_policy_args": GrPolicyArgs, "gr_mlp_net": GrMlpNet, "gr_mlp_args": GrMlpArgs,
+           "gr_ppo_loss_args": GrPpoLossArgs, "gr_adam_segment": GrAdamSegment, "gr_adam_args": GrAdamArgs,
+           "gr_transition_args": GrTransitionArgs}
+
+
 GR_POLICY_ACT_LRELU, GR_POLICY_ACT_ELU = 0, 1
 GR_POLICY_BF16, GR_POLICY_FP32 = 0, 1
 GR_POLICY_LRELU_PRESCALE = 0.505
@@ -223,135 +270,109 @@ GR_ERR_CAPACITY = -4
 GR_FAULT_NONE, GR_FAULT_OBST_NO_SIGNAL = 0, 1
 STATUS_TEXT = {GR_STATUS_OBST_WAIT_TIMEOUT: "a physics wave gave up waiting for its obstacle mask (stale mask used)"}
 
-EXPORTS = [
-    "gr_abi_version", "gr_source_sha256", "gr_config_default", "gr_config_size", "gr_create", "gr_destroy", "gr_last_error",
-    "gr_num_blocks", "gr_num_log_rows", "gr_log_finalize", "gr_bytes_per_env_step", "gr_bind_tracks", "gr_bind_obstacles", "gr_swap_terrain", "gr_bind_buffers", "gr_bind_obs_sink", "gr_init", "gr_reset",
-    "gr_step", "gr_observe", "gr_device_status", "gr_test_inject_fault", "gr_test_camera_slots", "gr_set_timing", "gr_read_timing", "gr_test_dynamics", "gr_test_math",
-    "gr_test_philox",
-    "gr_debug_read_stamps", "gr_debug_read_policy_stamps",
-    "gr_camera_config_default", "gr_camera_config_size", "gr_enable_camera", "gr_bind_camera_buffers",
-    "gr_camera_render", "gr_camera_bytes_per_env", "gr_policy_forward", "gr_policy_args_size", "gr_column_sum_partials", "gr_column_sum",
-    "gr_head_partials", "gr_head_forward", "gr_head_backward", "gr_mlp_in_partials", "gr_mlp_in_forward",
-    "gr_mlp_in_backward", "gr_ppo_loss_partials", "gr_ppo_loss_forward", "gr_ppo_loss_backward",
-    "gr_adam_prepare", "gr_adam_clip", "gr_adam_step", "gr_adam_clip_step", "gr_ppo_loss_forward_backward",
-    "gr_store_transition", "gr_episode_accumulate", "gr_gae", "gr_l2c2_mix",
-    "gr_ppo_loss_forward_loss", "gr_ppo_loss_backward_loss", "gr_adaptive_lr",
-    "gr_bn_scratch_doubles", "gr_bn_act_forward", "gr_bn_act_backward", "gr_stem1_scratch_doubles",
-    "gr_stem1_forward", "gr_stem1_backward", "gr_mlp_partials", "gr_mlp_forward", "gr_mlp_backward",
-    "gr_mlp_args_size", "gr_step_kernel_variant", "gr_terrain_reserve", "gr_terrain_stage", "gr_terrain_commit",
-    "gr_terrain_epoch", "gr_mlp_h1mask_words", "gr_stem12_backward", "gr_stem12_forward",
-    "gr_patch_wgrad_floats", "gr_patch_wgrad", "gr_bn_running_update", "gr_tsgemm", "gr_l2c2_mix_rows", "gr_tsgemm_bnact",
-    "gr_patch_wgrad_bnact", "gr_bn_stats", "gr_stem12_backward_w2_scratch_doubles", "gr_stem12_backward_w2",
-]
+# every entry point of include/gr.h: name -> (restype, argtypes).  tests/test_abi.py parses the header's prototypes and
+# compares them with this table parameter by parameter.
+vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+# the image-side arguments the stem entry points share (img, ld, offset, rows, nimg, pix, na, nb, conv w, c, BN w, BN b)
+_IMG = [vp, i64, i64, vp, i32, vp, i32, i32, vp, i32, vp, vp]
+SIGNATURES = {
+    "gr_abi_version": (C.c_int, []),
+    "gr_config_default": (C.c_int, [C.POINTER(GrConfig)]),
+    "gr_config_size": (C.c_size_t, []),
+    "gr_create": (C.c_int, [C.POINTER(GrConfig), C.POINTER(vp)]),
+    "gr_destroy": (C.c_int, [vp]),
+    "gr_last_error": (C.c_char_p, [vp]),
+    "gr_num_blocks": (C.c_int, [vp]),
+    "gr_num_log_rows": (C.c_int, [vp]),
+    "gr_log_finalize": (C.c_int, [vp, vp, vp, vp, vp]),
+    "gr_bytes_per_env_step": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "gr_bind_tracks": (C.c_int, [vp, vp, vp]),
+    "gr_bind_obstacles": (C.c_int, [vp, C.POINTER(GrObstacles)]),
+    "gr_swap_terrain": (C.c_int, [vp, vp, vp, vp, C.POINTER(GrObstacles), C.POINTER(GrObstacles), vp]),
+    "gr_terrain_reserve": (C.c_int, [vp, i32, i32, i32]),
+    "gr_terrain_stage": (C.c_int, [vp, vp, vp, C.POINTER(GrObstacles), vp]),
+    "gr_terrain_commit": (C.c_int, [vp, vp]),
+    "gr_terrain_epoch": (i64, [vp]),
+    "gr_mlp_h1mask_words": (i64, [i64, i32]),
+    "gr_bind_buffers": (C.c_int, [vp, C.POINTER(GrBuffers)]),
+    "gr_bind_obs_sink": (C.c_int, [vp, vp, vp, C.c_int]),
+    "gr_init": (C.c_int, [vp, vp]),
+    "gr_reset": (C.c_int, [vp, vp, vp]),
+    "gr_step": (C.c_int, [vp, vp, vp]),
+    "gr_observe": (C.c_int, [vp, vp]),
+    "gr_step_kernel_variant": (C.c_int, [vp]),
+    "gr_device_status": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_int, vp]),
+    "gr_source_sha256": (C.c_char_p, []),
+    "gr_test_inject_fault": (C.c_int, [vp, C.c_int]),
+    "gr_test_camera_slots": (C.c_int, [vp, i32]),
+    "gr_set_timing": (C.c_int, [vp, C.c_int]),
+    "gr_read_timing": (C.c_int, [vp, C.POINTER(f64), C.POINTER(i64)]),
+    "gr_test_dynamics": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 9 + [vp]),
+    "gr_test_math": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "gr_test_philox": (C.c_int, [vp, C.c_int] + [C.c_uint32] * 4 + [vp, vp]),
+    "gr_debug_read_stamps": (C.c_int, [vp, C.c_int]),
+    "gr_debug_read_policy_stamps": (C.c_int, [vp, C.c_int]),
+    "gr_camera_config_default": (C.c_int, [C.POINTER(GrCameraConfig)]),
+    "gr_camera_config_size": (C.c_size_t, []),
+    "gr_enable_camera": (C.c_int, [vp, C.POINTER(GrCameraConfig)]),
+    "gr_bind_camera_buffers": (C.c_int, [vp, C.POINTER(GrCameraBuffers)]),
+    "gr_camera_render": (C.c_int, [vp, C.c_int, vp, vp]),
+    "gr_camera_bytes_per_env": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "gr_policy_forward": (C.c_int, [C.POINTER(GrPolicyArgs), vp]),
+    "gr_policy_args_size": (C.c_size_t, []),
+    "gr_column_sum_partials": (C.c_int, [i64]),
+    "gr_column_sum": (C.c_int, [vp, C.c_int, i64, i32, vp, vp, vp]),
+    "gr_head_partials": (i64, [i64, i32, i32]),
+    "gr_head_forward": (C.c_int, [vp, i64, i32, vp, vp, i32, f32, vp, vp]),
+    "gr_head_backward": (C.c_int, [vp, vp, i64, i32, vp, i32, f32, vp, vp, vp, vp]),
+    "gr_mlp_in_partials": (i64, [i64, i32, i32]),
+    "gr_ppo_loss_partials": (i64, [i64]),
+    "gr_adam_prepare": (C.c_int, [vp, i32, C.POINTER(i32)]),
+    "gr_store_transition": (C.c_int, [C.POINTER(GrTransitionArgs), vp]),
+    "gr_ppo_loss_forward_loss": (C.c_int, [C.POINTER(GrPpoLossArgs), vp, vp, f32, vp, vp, vp, vp, vp]),
+    "gr_ppo_loss_backward_loss": (C.c_int, [C.POINTER(GrPpoLossArgs), vp, f32, vp, vp, vp, vp, vp]),
+    "gr_adaptive_lr": (C.c_int, [vp, vp, f64, f64, f64, vp]),
+    "gr_episode_accumulate": (C.c_int, [i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "gr_gae": (C.c_int, [i64, i32, f32, f32, vp, vp, vp, vp, i64, vp, vp, vp]),
+    "gr_l2c2_mix": (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
+    "gr_l2c2_mix_rows": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp]),
+    "gr_tsgemm_bnact": (C.c_int, [vp, i64, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp]),
+    "gr_patch_wgrad_bnact": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, i32, f32, vp]),
+    "gr_bn_stats": (C.c_int, [vp, i64, i32, f32, vp, vp, vp]),
+    "gr_adam_clip": (C.c_int, [C.POINTER(GrAdamArgs), f32, vp, vp]),
+    "gr_adam_step": (C.c_int, [C.POINTER(GrAdamArgs), vp]),
+    "gr_adam_clip_step": (C.c_int, [C.POINTER(GrAdamArgs), f32, vp, vp, vp, f64, f64, f64, vp]),
+    "gr_ppo_loss_forward_backward": (C.c_int, [C.POINTER(GrPpoLossArgs), vp, f32] + [vp] * 11),
+    "gr_ppo_loss_forward": (C.c_int, [C.POINTER(GrPpoLossArgs), vp, vp, vp]),
+    "gr_ppo_loss_backward": (C.c_int, [C.POINTER(GrPpoLossArgs), vp, vp, vp, vp, vp, vp]),
+    "gr_mlp_in_forward": (C.c_int, [vp, i64, i32, i32, vp, vp, i32, f32, vp, vp]),
+    "gr_mlp_in_backward": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, f32, vp, vp, vp]),
+    "gr_mlp_partials": (i64, [i64, i32, i32]),
+    "gr_mlp_forward": (C.c_int, [C.POINTER(GrMlpArgs), vp]),
+    "gr_mlp_backward": (C.c_int, [C.POINTER(GrMlpArgs), vp]),
+    "gr_mlp_args_size": (C.c_size_t, []),
+    "gr_bn_scratch_doubles": (i64, [i64, i32]),
+    "gr_bn_act_forward": (C.c_int, [vp, i64, i32, vp, vp, f32, i32, f32, vp, vp, vp, vp]),
+    "gr_bn_act_backward": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
+    "gr_stem1_scratch_doubles": (i64, [i32, i32, i32]),
+    "gr_stem1_forward": (C.c_int, _IMG + [f32, i32, f32, vp, i64, vp, vp, vp]),
+    "gr_stem1_backward": (C.c_int, _IMG + [vp, i32, f32, vp, i64, vp, vp, vp, vp, vp]),
+    "gr_patch_wgrad_floats": (i64, [i64, i32, i32]),
+    "gr_patch_wgrad": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, vp]),
+    "gr_bn_running_update": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, i32, i32, vp]),
+    "gr_tsgemm": (C.c_int, [vp, i64, vp, i32, vp, i64, i64, i32, i32, vp]),
+    "gr_stem12_forward": (C.c_int, _IMG + [f32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "gr_stem12_backward": (C.c_int, _IMG + [vp, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "gr_stem12_backward_w2_scratch_doubles": (i64, [i32]),
+    "gr_stem12_backward_w2": (C.c_int, _IMG + [vp, vp, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
 
 def _declare(lib):
-    vp = C.c_void_p
-    sig = {
-        "gr_abi_version": (C.c_int, []),
-        "gr_config_default": (C.c_int, [C.POINTER(GrConfig)]),
-        "gr_config_size": (C.c_size_t, []),
-        "gr_create": (C.c_int, [C.POINTER(GrConfig), C.POINTER(vp)]),
-        "gr_destroy": (C.c_int, [vp]),
-        "gr_last_error": (C.c_char_p, [vp]),
-        "gr_num_blocks": (C.c_int, [vp]),
-        "gr_num_log_rows": (C.c_int, [vp]),
-        "gr_log_finalize": (C.c_int, [vp, vp, vp, vp, vp]),
-        "gr_bytes_per_env_step": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "gr_bind_tracks": (C.c_int, [vp, vp, vp]),
-        "gr_bind_obstacles": (C.c_int, [vp, C.POINTER(GrObstacles)]),
-        "gr_swap_terrain": (C.c_int, [vp, vp, vp, vp, C.POINTER(GrObstacles), C.POINTER(GrObstacles), vp]),
-        "gr_terrain_reserve": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32]),
-        "gr_terrain_stage": (C.c_int, [vp, vp, vp, C.POINTER(GrObstacles), vp]),
-        "gr_terrain_commit": (C.c_int, [vp, vp]),
-        "gr_terrain_epoch": (C.c_int64, [vp]),
-        "gr_mlp_h1mask_words": (C.c_int64, [C.c_int64, C.c_int32]),
-        "gr_bind_buffers": (C.c_int, [vp, C.POINTER(GrBuffers)]),
-        "gr_bind_obs_sink": (C.c_int, [vp, vp, vp, C.c_int]),
-        "gr_init": (C.c_int, [vp, vp]),
-        "gr_reset": (C.c_int, [vp, vp, vp]),
-        "gr_step": (C.c_int, [vp, vp, vp]),
-        "gr_observe": (C.c_int, [vp, vp]),
-        "gr_step_kernel_variant": (C.c_int, [vp]),
-        "gr_device_status": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_int, vp]),
-        "gr_source_sha256": (C.c_char_p, []),
-        "gr_test_inject_fault": (C.c_int, [vp, C.c_int]),
-        "gr_test_camera_slots": (C.c_int, [vp, C.c_int32]),
-        "gr_set_timing": (C.c_int, [vp, C.c_int]),
-        "gr_read_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-        "gr_test_dynamics": (C.c_int, [vp, C.c_int, C.c_int] + [vp] * 9 + [vp]),
-        "gr_test_math": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
-        "gr_test_philox": (C.c_int, [vp, C.c_int] + [C.c_uint32] * 4 + [vp, vp]),
-        "gr_debug_read_stamps": (C.c_int, [vp, C.c_int]),
-        "gr_debug_read_policy_stamps": (C.c_int, [vp, C.c_int]),
-        "gr_camera_config_default": (C.c_int, [C.POINTER(GrCameraConfig)]),
-        "gr_camera_config_size": (C.c_size_t, []),
-        "gr_enable_camera": (C.c_int, [vp, C.POINTER(GrCameraConfig)]),
-        "gr_bind_camera_buffers": (C.c_int, [vp, C.POINTER(GrCameraBuffers)]),
-        "gr_camera_render": (C.c_int, [vp, C.c_int, vp, vp]),
-        "gr_camera_bytes_per_env": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "gr_policy_forward": (C.c_int, [C.POINTER(GrPolicyArgs), vp]),
-        "gr_policy_args_size": (C.c_size_t, []),
-        "gr_column_sum_partials": (C.c_int, [C.c_int64]),
-        "gr_column_sum": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int32, vp, vp, vp]),
-        "gr_head_partials": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-        "gr_head_forward": (C.c_int, [vp, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.c_float, vp, vp]),
-        "gr_head_backward": (C.c_int, [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, C.c_float, vp, vp, vp, vp]),
-        "gr_mlp_in_partials": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-        "gr_ppo_loss_partials": (C.c_int64, [C.c_int64]),
-        "gr_adam_prepare": (C.c_int, [vp, C.c_int32, vp]),
-        "gr_store_transition": (C.c_int, [vp, vp]),
-        "gr_ppo_loss_forward_loss": (C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
-        "gr_ppo_loss_backward_loss": (C.c_int, [vp, vp, C.c_float, vp, vp, vp, vp, vp]),
-        "gr_adaptive_lr": (C.c_int, [vp, vp, C.c_double, C.c_double, C.c_double, vp]),
-        "gr_episode_accumulate": (C.c_int, [C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp]),
-        "gr_gae": (C.c_int, [C.c_int64, C.c_int32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_int64, vp, vp, vp]),
-        "gr_l2c2_mix": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int32, vp, vp]),
-        "gr_l2c2_mix_rows": (C.c_int, [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]),
-        "gr_tsgemm_bnact": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp,
-                                      vp, vp, C.c_int32, C.c_float, vp]),
-        "gr_patch_wgrad_bnact": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp,
-                                           vp, vp, C.c_int32, C.c_float, vp]),
-        "gr_bn_stats": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_float, vp, vp, vp]),
-        "gr_adam_clip": (C.c_int, [vp, C.c_float, vp, vp]),
-        "gr_adam_step": (C.c_int, [vp, vp]),
-        "gr_adam_clip_step": (C.c_int, [vp, C.c_float, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp]),
-        "gr_ppo_loss_forward_backward": (C.c_int, [vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "gr_ppo_loss_forward": (C.c_int, [vp, vp, vp, vp]),
-        "gr_ppo_loss_backward": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
-        "gr_mlp_in_forward": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_float, vp, vp]),
-        "gr_mlp_in_backward": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, vp,
-                                         vp]),
-        "gr_mlp_partials": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-        "gr_mlp_forward": (C.c_int, [vp, vp]),
-        "gr_mlp_backward": (C.c_int, [vp, vp]),
-        "gr_mlp_args_size": (C.c_size_t, []),
-        "gr_bn_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
-        "gr_bn_act_forward": (C.c_int, [vp, C.c_int64, C.c_int32, vp, vp, C.c_float, C.c_int32, C.c_float, vp, vp, vp,
-                                        vp]),
-        "gr_bn_act_backward": (C.c_int, [vp, vp, C.c_int64, C.c_int32, vp, vp, vp, C.c_int32, C.c_float, vp, vp, vp,
-                                         vp, vp]),
-        "gr_stem1_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
-        "gr_stem1_forward": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32,
-                                       vp, vp, C.c_float, C.c_int32, C.c_float, vp, C.c_int64, vp, vp, vp]),
-        "gr_stem1_backward": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32,
-                                        vp, vp, vp, C.c_int32, C.c_float, vp, C.c_int64, vp, vp, vp, vp, vp]),
-        "gr_patch_wgrad_floats": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-        "gr_patch_wgrad": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]),
-        "gr_bn_running_update": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, vp]),
-        "gr_tsgemm": (C.c_int, [vp, C.c_int64, vp, C.c_int32, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp]),
-        "gr_stem12_forward": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32,
-                                        vp, vp, C.c_float, C.c_int32, C.c_float, vp, C.c_int32, vp, vp, vp, vp, vp, vp]),
-        "gr_stem12_backward": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32,
-                                         vp, vp, vp, C.c_int32, C.c_float, vp, C.c_int32, vp, vp, vp, vp, vp, vp]),
-        "gr_stem12_backward_w2_scratch_doubles": (C.c_int64, [C.c_int32]),
-        "gr_stem12_backward_w2": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp,
-                                            C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_float, vp, C.c_int32, vp, vp, vp,
-                                            vp, vp, vp, vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         if not hasattr(lib, name) and os.environ.get("GR_LIB_PATH"):
             continue  # an older timing build (GR_LIB_PATH) may predate an entry point
         f = getattr(lib, name)
@@ -405,11 +426,8 @@ def load(path: str | None = None):
     if lib.gr_policy_args_size() != C.sizeof(GrPolicyArgs):
         raise RuntimeError(f"gr_policy_args size mismatch: C {lib.gr_policy_args_size()} vs ctypes "
                            f"{C.sizeof(GrPolicyArgs)}")
-    if hasattr(lib, "gr_mlp_args_size"):
-        from .rsl_rl.linear import GrMlpArgs
-
-        if lib.gr_mlp_args_size() != C.sizeof(GrMlpArgs):
-            raise RuntimeError("gr_mlp_args size mismatch between libgr.so and the ctypes mirror")
+    if hasattr(lib, "gr_mlp_args_size") and lib.gr_mlp_args_size() != C.sizeof(GrMlpArgs):
+        raise RuntimeError("gr_mlp_args size mismatch between libgr.so and the ctypes mirror")
     if path is None:
         _lib = lib
     return lib
@@ -417,38 +435,39 @@ def load(path: str | None = None):
 
 def default_config() -> GrConfig:
     cfg = GrConfig()
-    rc = load().gr_config_default(C.byref(cfg))
-    if rc != 0:
-        raise RuntimeError("gr_config_default failed")
+    call("gr_config_default", C.byref(cfg))
     return cfg
 
 
 def default_camera_config() -> GrCameraConfig:
     cfg = GrCameraConfig()
-    rc = load().gr_camera_config_default(C.byref(cfg))
-    if rc != 0:
-        raise RuntimeError("gr_camera_config_default failed")
+    call("gr_camera_config_default", C.byref(cfg))
     return cfg
 
 
-def check(lib, ctx, rc: int, what: str):
+def check(name: str, rc: int, ctx=None):
+    """Raise for a non-zero status of entry point `name`, with the context's gr_last_error when there is one."""
     if rc != 0:
-        msg = lib.gr_last_error(ctx) if ctx else b""
-        raise RuntimeError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
+        msg = f"{name} failed (status {rc})"
+        raise RuntimeError(msg if ctx is None else f"{msg}: {load().gr_last_error(ctx).decode()}")
 
 
-_RAW_STREAM = None
+def call(name: str, *args, ctx=None):
+    """The status-returning entry point `name` on the loaded library (ctx: a gr_ctx handle, passed first); raises
+    RuntimeError for a non-zero status."""
+    f = getattr(_lib or load(), name)
+    rc = f(*args) if ctx is None else f(ctx, *args)
+    if rc != 0:
+        check(name, rc, ctx)
+
+
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (torch's own raw-stream accessor)
 
 
 def raw_stream(device) -> int:
     """The raw handle of `device`'s current HIP stream for the C ABI's `stream` argument: torch's accessor when the
     device has an index (torch.cuda.current_stream(device) builds a Stream object under a device guard per call)."""
-    global _RAW_STREAM
-    import torch
-
-    if _RAW_STREAM is None:
-        _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", False)
     index = device.index if isinstance(device, torch.device) else None
-    if _RAW_STREAM and index is not None:
+    if _RAW_STREAM is not None and index is not None:
         return _RAW_STREAM(index)
     return torch.cuda.current_stream(device).cuda_stream

@@ -32,9 +32,6 @@ LOG_RING = 64
 REGEN_STAMPS = None
 
 
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # (torch's own raw-stream accessor)
-
-
 def _stamp(label):
     if REGEN_STAMPS is not None:
         REGEN_STAMPS.append((label, time.perf_counter()))
@@ -73,7 +70,7 @@ class _EpisodeLog(Mapping):
                 out = torch.empty(_abi.LOG_SLOTS, dtype=torch.float32, device=env.device)
                 pv = prev._vals.data_ptr() if prev is not None and prev._vals is not None else None
                 env._call("gr_log_finalize", env._log_slab[lg._k % LOG_RING].data_ptr(), pv, out.data_ptr(),
-                          env._stream())
+                          _abi.raw_stream(env.device))
                 if lg._empty_reset:
                     # the reference's _reset_idx over no envs (manager_based_diff_rl_env.py:362-407): the means
                     # over the reset envs are torch.mean of an empty set (NaN), the termination counts 0
@@ -119,7 +116,7 @@ class RacingEnv:
         dev = self.device
 
         ctx = C.c_void_p()
-        _abi.check(self._lib, None, self._lib.gr_create(C.byref(self._gcfg), C.byref(ctx)), "gr_create")
+        _abi.call("gr_create", C.byref(self._gcfg), C.byref(ctx))
         self._ctx = ctx
 
         # ---- track table + obstacles (host-generated, then device-resident) ----
@@ -191,7 +188,7 @@ class RacingEnv:
         self._last_img = None
         # startup (gr_init): nominal state, startup DR events, initial terrain levels
         self._bind(0)
-        self._call("gr_init", self._stream())
+        self._call("gr_init", _abi.raw_stream(self.device))
         self._calls, self._cur = 1, 1  # gr_init wrote output set 1 (binding 0); counters zeroed
 
     # ------------------------------------------------------------------ terrain
@@ -299,10 +296,10 @@ class RacingEnv:
         if not self._resident:
             self._reserve_terrain(obst)
         pin = self._pin_generation(gates, recs, obst)
-        rc = self._stage(pin, obst, self._stream())
+        rc = self._stage(pin, obst, _abi.raw_stream(self.device))
         if rc == _abi.GR_ERR_CAPACITY:
             self._reserve_terrain(obst)
-            rc = self._stage(pin, obst, self._stream())
+            rc = self._stage(pin, obst, _abi.raw_stream(self.device))
         if rc != 0:
             raise RuntimeError(f"gr_terrain_stage failed (status {rc}): {self._lib.gr_last_error(self._ctx).decode()}")
         # the upload is a raw hipMemcpyAsync that torch's pinned-memory cache does not track: the set is released only
@@ -323,7 +320,7 @@ class RacingEnv:
     def _commit(self, pin, gates, recs, obst):
         """gr_terrain_commit on the env's stream; the generation's host arrays become the env's track_gates /
         track_records / obstacle_table."""
-        self._call("gr_terrain_commit", self._stream())
+        self._call("gr_terrain_commit", _abi.raw_stream(self.device))
         _stamp("commit_call")
         # the replaced generation's host objects (and a fresh pin set, _stage_now) are released by the builder when
         # it starts the next build, not here: no host free in the interval step (nor in its graph capture)
@@ -506,21 +503,12 @@ class RacingEnv:
 
     def _render(self, mode: int, mask_ptr=None):
         if self.camera is not None:
-            self._call("gr_camera_render", mode, mask_ptr, self._stream())
-
-    def _stream(self):
-        # the raw handle of the device's current stream: torch.cuda.current_stream(device) builds a Stream object
-        # under a device guard on every env call (a few µs of each step's host time)
-        if _RAW_STREAM is not None and self.device.index is not None:
-            return _RAW_STREAM(self.device.index)
-        return torch.cuda.current_stream(self.device).cuda_stream
+            self._call("gr_camera_render", mode, mask_ptr, _abi.raw_stream(self.device))
 
     def _call(self, name, *args):
         if torch.cuda.is_current_stream_capturing():  # a graph now holds this epoch's terrain arrays (_reserve_terrain)
             self._captured_epoch = self.terrain_epoch
-        rc = getattr(self._lib, name)(self._ctx, *args)
-        if rc != 0:
-            raise RuntimeError(f"{name} failed (status {rc}): {self._lib.gr_last_error(self._ctx).decode()}")
+        _abi.call(name, *args, ctx=self._ctx)
 
     def _advance(self, out_set: dict | None = None, prev_set: dict | None = None):
         """Bind the next output set + log slab; returns (output set, extras["log"] of this call)."""
@@ -613,14 +601,14 @@ class RacingEnv:
         """The step_kernel instantiation gr_step launches with the current bindings (gr_step_kernel_variant)."""
         v = self._lib.gr_step_kernel_variant(self._ctx)
         if v < 0:
-            raise RuntimeError(f"gr_step_kernel_variant failed (status {v})")
+            _abi.check("gr_step_kernel_variant", v)
         return _abi.STEP_KERNEL_NAMES[v]
 
     def device_status(self, clear: bool = True) -> int:
         """gr_device_status: the GR_STATUS_* bits the step kernels raised since the last clear (synchronises the
         env's stream)."""
         st = C.c_uint32()
-        self._call("gr_device_status", C.byref(st), int(bool(clear)), self._stream())
+        self._call("gr_device_status", C.byref(st), int(bool(clear)), _abi.raw_stream(self.device))
         return st.value
 
     def check_device_status(self):
@@ -672,7 +660,7 @@ class RacingEnv:
         if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous() or a.data_ptr() % 16:
             a = a.to(device=self.device, dtype=torch.float32).contiguous()
         out, log = self._advance()
-        self._call("gr_step", a.data_ptr(), self._stream())
+        self._call("gr_step", a.data_ptr(), _abi.raw_stream(self.device))
         self._render(_abi.GR_CAM_STEP)
         self.common_step_counter += 1
         self.extras = {"log": log}
@@ -739,7 +727,7 @@ class RacingEnv:
             out = out_set
         log._empty_reset = empty
         mp = mask_t.data_ptr() if mask_t is not None else None
-        self._call("gr_reset", mp, self._stream())
+        self._call("gr_reset", mp, _abi.raw_stream(self.device))
         self._render(_abi.GR_CAM_RESET, mp)
         self.extras = {"log": log}
         return self._obs_dict(out), self.extras
@@ -793,14 +781,14 @@ class RacingEnv:
     def observe(self) -> dict:
         """ObservationManager.compute(): fresh observation noise, no state change."""
         out, _ = self._advance()
-        self._call("gr_observe", self._stream())
+        self._call("gr_observe", _abi.raw_stream(self.device))
         self._render(_abi.GR_CAM_OBSERVE)
         return self._obs_dict(out)
 
     def _observe_after(self, prev_set: dict):
         """observe() whose previous rows (the last action the rows carry) are prev_set's."""
         self._advance(prev_set=prev_set)
-        self._call("gr_observe", self._stream())
+        self._call("gr_observe", _abi.raw_stream(self.device))
 
     def seed(self, seed: int = -1) -> int:
         return seed

@@ -28,28 +28,10 @@ import ctypes as C
 
 import torch
 
+from .. import _abi
+from .._abi import GrAdamArgs, GrAdamSegment
+
 MAX_SEGMENTS = 64  # GR_ADAM_MAX_SEGMENTS (include/gr.h)
-
-
-class GrAdamSegment(C.Structure):
-    """Mirror of gr_adam_segment (include/gr.h)."""
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("numel", C.c_int64), ("step_slot", C.c_int32), ("block_start", C.c_int32)]
-
-
-class GrAdamArgs(C.Structure):
-    """Mirror of gr_adam_args (include/gr.h)."""
-    _fields_ = [("nseg", C.c_int32), ("nblocks", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double),
-                ("beta2", C.c_double), ("eps", C.c_float), ("pad", C.c_int32), ("lr_ptr", C.c_void_p),
-                ("step", C.c_void_p), ("coef", C.c_void_p), ("part", C.c_void_p), ("seg", C.c_void_p)]
-
-
-def _call(name, *args):
-    from .. import _abi
-
-    rc = getattr(_abi.load(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed (status {rc})")
 
 
 def flat_adam_ok(params) -> bool:
@@ -120,7 +102,7 @@ class FlatAdam(torch.optim.Optimizer):
                 t.numel, t.step_slot = p.numel(), i
                 self._register(p)
             nblocks = C.c_int32()
-            _call("gr_adam_prepare", C.addressof(table), len(ps), C.byref(nblocks))
+            _abi.call("gr_adam_prepare", table, len(ps), C.byref(nblocks))
             dev = self._m.device
             self._table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
             self._part = torch.empty(nblocks.value, device=dev, dtype=torch.float64)
@@ -137,11 +119,6 @@ class FlatAdam(torch.optim.Optimizer):
             a.lr = float(lr)
         return a
 
-    def _stream(self):
-        from .. import _abi
-
-        return _abi.raw_stream(self._m.device)
-
     @torch.no_grad()
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         """nn.utils.clip_grad_norm_(params, max_norm) over the parameters with a gradient; returns the norm
@@ -149,7 +126,7 @@ class FlatAdam(torch.optim.Optimizer):
         a = self._args()
         if a is None:
             return self._norm[0].zero_()
-        _call("gr_adam_clip", C.addressof(a), C.c_float(float(max_norm)), self._norm.data_ptr(), self._stream())
+        _abi.call("gr_adam_clip", C.byref(a), float(max_norm), self._norm.data_ptr(), _abi.raw_stream(self._m.device))
         return self._norm[0]
 
     @torch.no_grad()
@@ -160,7 +137,7 @@ class FlatAdam(torch.optim.Optimizer):
                 loss = closure()
         a = self._args()
         if a is not None:
-            _call("gr_adam_step", C.addressof(a), self._stream())
+            _abi.call("gr_adam_step", C.byref(a), _abi.raw_stream(self._m.device))
             # the kernel wrote the parameters through raw pointers: bump their version counters as torch's in-place
             # Adam does, so caches keyed on them (the fused rollout inference's packed weights) see the update
             for p in self.param_groups[0]["params"]:
@@ -180,9 +157,9 @@ class FlatAdam(torch.optim.Optimizer):
         lr = self.param_groups[0]["lr"]
         if kl is not None and not (torch.is_tensor(lr) and lr.data_ptr() == a.lr_ptr):
             raise ValueError("clip_and_step: the adaptive rule needs the group's rate as a device tensor")
-        _call("gr_adam_clip_step", C.addressof(a), C.c_float(float(max_norm)), self._norm.data_ptr(),
-              kl.data_ptr() if kl is not None else None, lr.data_ptr() if kl is not None else None,
-              C.c_double(float(desired_kl or 0.0)), C.c_double(lr_min), C.c_double(lr_max), self._stream())
+        _abi.call("gr_adam_clip_step", C.byref(a), float(max_norm), self._norm.data_ptr(),
+                  kl.data_ptr() if kl is not None else None, lr.data_ptr() if kl is not None else None,
+                  float(desired_kl or 0.0), lr_min, lr_max, _abi.raw_stream(self._m.device))
         for p in self.param_groups[0]["params"]:
             if p.grad is not None:
                 torch.autograd.graph.increment_version(p)

@@ -11,8 +11,6 @@ statistics) stays on torch's op.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -30,23 +28,44 @@ def _act_code(act: nn.Module):
     return None
 
 
-def _stream(x):
-    return C.c_void_p(_abi.raw_stream(x.device))
+def _scratch(device, query: str, *dims) -> torch.Tensor:
+    """The float64 workspace of a launch, its size asked of libgr.so (`query`: a gr_*_scratch_doubles entry point)."""
+    return torch.empty(int(getattr(_abi.load(), query)(*dims)), device=device, dtype=torch.float64)
+
+
+def bn_stats(x: torch.Tensor, eps: float) -> torch.Tensor:
+    """The training-mode BatchNorm statistics [4, C] of rows x [M, C] (gr_bn_stats: gr_bn_act_forward's own)."""
+    m, c = x.shape
+    stats = torch.empty(4, c, device=x.device, dtype=torch.float32)
+    part = _scratch(x.device, "gr_bn_scratch_doubles", m, c)
+    _abi.call("gr_bn_stats", x.data_ptr(), m, c, float(eps), stats.data_ptr(), part.data_ptr(),
+              _abi.raw_stream(x.device))
+    return stats
+
+
+def _bn_act_backward(x, gy, w, b, stats, act, slope):
+    """gr_bn_act_backward -> (gx, gw, gb)."""
+    m, c = x.shape
+    gx = torch.empty_like(x)
+    gw = torch.empty(c, device=x.device, dtype=torch.float32)
+    gb = torch.empty(c, device=x.device, dtype=torch.float32)
+    part = _scratch(x.device, "gr_bn_scratch_doubles", m, c)
+    _abi.call("gr_bn_act_backward", x.data_ptr(), gy.data_ptr(), m, c, w.data_ptr(), b.data_ptr(), stats.data_ptr(),
+              act, float(slope), gx.data_ptr(), gw.data_ptr(), gb.data_ptr(), part.data_ptr(),
+              _abi.raw_stream(x.device))
+    return gx, gw, gb
 
 
 class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, act, slope):
-        lib = _abi.load()
         m, c = x.shape
         y = torch.empty_like(x)
         stats = torch.empty(4, c, device=x.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_bn_scratch_doubles(m, c)), device=x.device, dtype=torch.float64)
+        part = _scratch(x.device, "gr_bn_scratch_doubles", m, c)
         w, b = weight.detach().contiguous(), bias.detach().contiguous()
-        rc = lib.gr_bn_act_forward(x.data_ptr(), m, c, w.data_ptr(), b.data_ptr(), float(eps), act, float(slope),
-                                   y.data_ptr(), stats.data_ptr(), part.data_ptr(), _stream(x))
-        if rc != 0:
-            raise RuntimeError(f"gr_bn_act_forward failed (status {rc})")
+        _abi.call("gr_bn_act_forward", x.data_ptr(), m, c, w.data_ptr(), b.data_ptr(), float(eps), act, float(slope),
+                  y.data_ptr(), stats.data_ptr(), part.data_ptr(), _abi.raw_stream(x.device))
         ctx.save_for_backward(x, w, b, stats)
         ctx.act, ctx.slope = act, slope
         ctx.mark_non_differentiable(stats)
@@ -54,20 +73,8 @@ class _BatchNormAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gstats):
-        lib = _abi.load()
         x, w, b, stats = ctx.saved_tensors
-        m, c = x.shape
-        gy = gy.contiguous()
-        gx = torch.empty_like(x)
-        gw = torch.empty(c, device=x.device, dtype=torch.float32)
-        gb = torch.empty(c, device=x.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_bn_scratch_doubles(m, c)), device=x.device, dtype=torch.float64)
-        rc = lib.gr_bn_act_backward(x.data_ptr(), gy.data_ptr(), m, c, w.data_ptr(), b.data_ptr(), stats.data_ptr(),
-                                    ctx.act, float(ctx.slope), gx.data_ptr(), gw.data_ptr(), gb.data_ptr(),
-                                    part.data_ptr(), _stream(x))
-        if rc != 0:
-            raise RuntimeError(f"gr_bn_act_backward failed (status {rc})")
-        return gx, gw, gb, None, None, None
+        return _bn_act_backward(x, gy.contiguous(), w, b, stats, ctx.act, ctx.slope) + (None, None, None)
 
 
 def fused_applicable(bn: nn.BatchNorm2d, act: nn.Module, x: torch.Tensor) -> bool:
@@ -89,6 +96,15 @@ def batch_norm_act(bn: nn.BatchNorm2d, act: nn.Module, x: torch.Tensor, uses: in
     return y
 
 
+def _stem_args(img, rows, pix, na, nb, w, bw, bb):
+    """(images in the batch, the image-side arguments every gr_stem1_* / gr_stem12_* entry point starts with): the image
+    rows and their stride, the batch's row indices into them (or all of them), the pixel table, the conv weight [c, 9]
+    and the BatchNorm's affine pair."""
+    nimg = img.shape[0] if rows is None else rows.numel()
+    return nimg, (img.data_ptr(), img.stride(0), 0, rows.data_ptr() if rows is not None else None, nimg,
+                  pix.data_ptr(), na, nb, w.data_ptr(), w.shape[0], bw.data_ptr(), bb.data_ptr())
+
+
 class _Stem1(torch.autograd.Function):
     """Conv2d(1, C, 3, stride 3) -> BatchNorm2d (batch statistics) -> act from the depth images (gr_stem1_*).
     Returns the nimg x na table-a rows only (the next conv's input as it is): the nimg x nb table-b rows enter the
@@ -96,19 +112,15 @@ class _Stem1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, conv_w, bn_w, bn_b, pix, na, nb, eps, act, slope, rows=None):
-        lib = _abi.load()
-        nimg = img.shape[0] if rows is None else rows.numel()
         c = conv_w.shape[0]
-        y = torch.empty(nimg * na, c, device=img.device, dtype=torch.float32)
-        stats = torch.empty(4, c, device=img.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_stem1_scratch_doubles(nimg, na + nb, c)), device=img.device, dtype=torch.float64)
         w = conv_w.detach().reshape(c, 9).contiguous()
         bw, bb = bn_w.detach().contiguous(), bn_b.detach().contiguous()
-        rc = lib.gr_stem1_forward(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, pix.data_ptr(), na, nb,
-                                  w.data_ptr(), c, bw.data_ptr(), bb.data_ptr(), float(eps), act, float(slope),
-                                  y.data_ptr(), nimg * na, stats.data_ptr(), part.data_ptr(), _stream(img))
-        if rc != 0:
-            raise RuntimeError(f"gr_stem1_forward failed (status {rc})")
+        nimg, image = _stem_args(img, rows, pix, na, nb, w, bw, bb)
+        y = torch.empty(nimg * na, c, device=img.device, dtype=torch.float32)
+        stats = torch.empty(4, c, device=img.device, dtype=torch.float32)
+        part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, c)
+        _abi.call("gr_stem1_forward", *image, float(eps), act, float(slope), y.data_ptr(), nimg * na, stats.data_ptr(),
+                  part.data_ptr(), _abi.raw_stream(img.device))
         ctx.save_for_backward(img, w, bw, bb, stats)
         ctx.pix = pix  # a constant table (possibly made under inference mode): kept as an attribute
         ctx.rows = rows  # (the batch's row indices into img, or None)
@@ -120,24 +132,17 @@ class _Stem1(torch.autograd.Function):
     def backward(ctx, gy, _gstats):
         if ctx.needs_input_grad[0]:
             raise RuntimeError("the fused stem computes no gradient for the image")
-        lib = _abi.load()
         img, w, bw, bb, stats = ctx.saved_tensors
-        pix = ctx.pix
         na, nb, act, slope, wshape = ctx.args
-        rows = ctx.rows
-        nimg, c = (img.shape[0] if rows is None else rows.numel()), w.shape[0]
+        nimg, image = _stem_args(img, ctx.rows, ctx.pix, na, nb, w, bw, bb)
+        c = w.shape[0]
         gy = gy.contiguous()
         gconv = torch.empty(c, 9, device=img.device, dtype=torch.float32)
         gbw = torch.empty(c, device=img.device, dtype=torch.float32)
         gbb = torch.empty(c, device=img.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_stem1_scratch_doubles(nimg, na + nb, c)), device=img.device, dtype=torch.float64)
-        rc = lib.gr_stem1_backward(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, pix.data_ptr(), na, nb,
-                                   w.data_ptr(), c, bw.data_ptr(), bb.data_ptr(), stats.data_ptr(), act, float(slope),
-                                   gy.data_ptr(),
-                                   gy.shape[0], gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(),
-                                   _stream(img))
-        if rc != 0:
-            raise RuntimeError(f"gr_stem1_backward failed (status {rc})")
+        part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, c)
+        _abi.call("gr_stem1_backward", *image, stats.data_ptr(), act, float(slope), gy.data_ptr(), gy.shape[0],
+                  gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), _abi.raw_stream(img.device))
         return None, gconv.view(wshape), gbw, gbb, None, None, None, None, None, None, None
 
 
@@ -165,8 +170,9 @@ class _Stem12(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, conv_w, bn_w, bn_b, w2, pix, na, nb, eps, act, slope, fused_forward=True, rows=None,
                 keep_y=True):
-        lib = _abi.load()
-        nimg = img.shape[0] if rows is None else rows.numel()
+        w = conv_w.detach().reshape(16, 9).contiguous()
+        bw, bb = bn_w.detach().contiguous(), bn_b.detach().contiguous()
+        nimg, image = _stem_args(img, rows, pix, na, nb, w, bw, bb)
         # (keep_y False: no backward will run, so y1 — kept only for conv2's weight gradient — is not stored; nor when
         # that gradient is formed inside the first block's backward)
         w2_path = _w2_path(fused_forward, na)
@@ -174,29 +180,23 @@ class _Stem12(torch.autograd.Function):
         keep_y = (keep_y and not w2_path) or not fused_forward
         y = torch.empty(nimg * na if keep_y else 0, 16, device=img.device, dtype=torch.float32)
         stats = torch.empty(4, 16, device=img.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_stem1_scratch_doubles(nimg, na + nb, 16)), device=img.device, dtype=torch.float64)
-        w = conv_w.detach().reshape(16, 9).contiguous()
-        bw, bb = bn_w.detach().contiguous(), bn_b.detach().contiguous()
+        part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, 16)
         w2d = w2.detach()
         # the statistics pass's pixel moments, when the backward will take conv1's A2 / A3 sums from them
         mom = torch.empty(64 if (w2_path and STEM12_MOMENTS and backward_follows) else 0, device=img.device,
                           dtype=torch.float64)
+        stream = _abi.raw_stream(img.device)
         if fused_forward:
             # conv2 inside the first block's apply pass: w2f[j][g][o][v] = W2[o][j * 16 + 4 g + v]
             w2f = w2d.reshape(32, 9, 4, 4).permute(1, 2, 0, 3).contiguous()
             z2 = torch.empty(nimg * (na // 9), 32, device=img.device, dtype=torch.float32)
-            rc = lib.gr_stem12_forward(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, pix.data_ptr(), na, nb,
-                                       w.data_ptr(), 16, bw.data_ptr(), bb.data_ptr(), float(eps), act, float(slope),
-                                       w2f.data_ptr(),
-                                       na // 9, y.data_ptr() if keep_y else None, z2.data_ptr(), stats.data_ptr(),
-                                       mom.data_ptr() if mom.numel() else None, part.data_ptr(), _stream(img))
+            _abi.call("gr_stem12_forward", *image, float(eps), act, float(slope), w2f.data_ptr(), na // 9,
+                      y.data_ptr() if keep_y else None, z2.data_ptr(), stats.data_ptr(),
+                      mom.data_ptr() if mom.numel() else None, part.data_ptr(), stream)
         else:  # the first block's kernels, then conv2 as a GEMM (the A/B reference of the fused forward)
-            rc = lib.gr_stem1_forward(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, pix.data_ptr(), na, nb,
-                                      w.data_ptr(), 16, bw.data_ptr(), bb.data_ptr(), float(eps), act, float(slope),
-                                      y.data_ptr(), nimg * na, stats.data_ptr(), part.data_ptr(), _stream(img))
-            z2 = y.view(-1, 144) @ w2d.t() if rc == 0 else None
-        if rc != 0:
-            raise RuntimeError(f"gr_stem12_forward failed (status {rc})")
+            _abi.call("gr_stem1_forward", *image, float(eps), act, float(slope), y.data_ptr(), nimg * na,
+                      stats.data_ptr(), part.data_ptr(), stream)
+            z2 = y.view(-1, 144) @ w2d.t()
         ctx.save_for_backward(img, w, bw, bb, stats, y, w2d, mom)
         ctx.pix = pix
         ctx.rows = rows
@@ -209,11 +209,9 @@ class _Stem12(torch.autograd.Function):
     def backward(ctx, gz2, _gstats):
         if ctx.needs_input_grad[0]:
             raise RuntimeError("the fused stem computes no gradient for the image")
-        lib = _abi.load()
         img, w, bw, bb, stats, y, w2d, mom = ctx.saved_tensors
         na, nb, act, slope, wshape = ctx.args
-        rows = ctx.rows
-        nimg = img.shape[0] if rows is None else rows.numel()
+        nimg, image = _stem_args(img, ctx.rows, ctx.pix, na, nb, w, bw, bb)
         gz2 = gz2.contiguous()
         if gz2.data_ptr() % 16:
             gz2 = gz2.clone()
@@ -222,32 +220,24 @@ class _Stem12(torch.autograd.Function):
         gconv = torch.empty(16, 9, device=img.device, dtype=torch.float32)
         gbw = torch.empty(16, device=img.device, dtype=torch.float32)
         gbb = torch.empty(16, device=img.device, dtype=torch.float32)
+        stream = _abi.raw_stream(img.device)
         if ctx.w2_path:  # the first block's backward with conv2's dgrad and wgrad (y1 recomputed)
             gw2 = torch.empty(32, 144, device=img.device, dtype=torch.float32)
-            part = torch.empty(int(lib.gr_stem12_backward_w2_scratch_doubles(nimg)), device=img.device,
-                               dtype=torch.float64)
-            rc = lib.gr_stem12_backward_w2(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, ctx.pix.data_ptr(),
-                                           na, nb, w.data_ptr(), 16, bw.data_ptr(), bb.data_ptr(), stats.data_ptr(),
-                                           mom.data_ptr() if mom.numel() else None, act,
-                                           float(slope), gz2.data_ptr(), na // 9, w2t.data_ptr(), gconv.data_ptr(),
-                                           gbw.data_ptr(), gbb.data_ptr(), gw2.data_ptr(), part.data_ptr(), _stream(img))
-            if rc != 0:
-                raise RuntimeError(f"gr_stem12_backward_w2 failed (status {rc})")
-            return (None, gconv.view(wshape), gbw, gbb, gw2 if ctx.needs_input_grad[4] else None, None, None, None,
-                    None, None, None, None, None, None)
-        gw2 = None
-        if ctx.needs_input_grad[4]:  # conv2's weight: gz2^T y1 patches (gr_patch_wgrad: MFMA, fixed-order sums)
-            from .linear import tall_wgrad
+            part = _scratch(img.device, "gr_stem12_backward_w2_scratch_doubles", nimg)
+            _abi.call("gr_stem12_backward_w2", *image, stats.data_ptr(), mom.data_ptr() if mom.numel() else None, act,
+                      float(slope), gz2.data_ptr(), na // 9, w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(),
+                      gbb.data_ptr(), gw2.data_ptr(), part.data_ptr(), stream)
+            if not ctx.needs_input_grad[4]:
+                gw2 = None
+        else:
+            gw2 = None
+            if ctx.needs_input_grad[4]:  # conv2's weight: gz2^T y1 patches (gr_patch_wgrad: MFMA, fixed-order sums)
+                from .linear import tall_wgrad
 
-            gw2 = tall_wgrad(gz2, y.view(y.shape[0] // 9, 144))
-        part = torch.empty(int(lib.gr_stem1_scratch_doubles(nimg, na + nb, 16)), device=img.device, dtype=torch.float64)
-        rc = lib.gr_stem12_backward(img.data_ptr(), img.stride(0), 0, _rows_ptr(rows), nimg, ctx.pix.data_ptr(), na, nb,
-                                    w.data_ptr(), 16, bw.data_ptr(), bb.data_ptr(), stats.data_ptr(), act, float(slope),
-                                    gz2.data_ptr(),
-                                    na // 9, w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(),
-                                    part.data_ptr(), _stream(img))
-        if rc != 0:
-            raise RuntimeError(f"gr_stem12_backward failed (status {rc})")
+                gw2 = tall_wgrad(gz2, y.view(y.shape[0] // 9, 144))
+            part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, 16)
+            _abi.call("gr_stem12_backward", *image, stats.data_ptr(), act, float(slope), gz2.data_ptr(), na // 9,
+                      w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), stream)
         return None, gconv.view(wshape), gbw, gbb, gw2, None, None, None, None, None, None, None, None, None
 
 
@@ -262,21 +252,14 @@ class _BnActPatchGemm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bn_w, bn_b, w, eps, act, slope):
-        lib = _abi.load()
         m, c = z.shape
         n, k = w.shape
-        stats = torch.empty(4, c, device=z.device, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_bn_scratch_doubles(m, c)), device=z.device, dtype=torch.float64)
-        rc = lib.gr_bn_stats(z.data_ptr(), m, c, float(eps), stats.data_ptr(), part.data_ptr(), _stream(z))
-        if rc != 0:
-            raise RuntimeError(f"gr_bn_stats failed (status {rc})")
+        stats = bn_stats(z, eps)
         bw, bb, wd = bn_w.detach().contiguous(), bn_b.detach().contiguous(), w.detach().contiguous()
         mp = m * c // k
         y = torch.empty(mp, n, device=z.device, dtype=torch.float32)
-        rc = lib.gr_tsgemm_bnact(z.data_ptr(), k, wd.data_ptr(), y.data_ptr(), n, mp, k, n, c, stats.data_ptr(),
-                                 bw.data_ptr(), bb.data_ptr(), act, float(slope), _stream(z))
-        if rc != 0:
-            raise RuntimeError(f"gr_tsgemm_bnact failed (status {rc})")
+        _abi.call("gr_tsgemm_bnact", z.data_ptr(), k, wd.data_ptr(), y.data_ptr(), n, mp, k, n, c, stats.data_ptr(),
+                  bw.data_ptr(), bb.data_ptr(), act, float(slope), _abi.raw_stream(z.device))
         ctx.save_for_backward(z, bw, bb, stats, wd)
         ctx.act, ctx.slope = act, slope
         ctx.mark_non_differentiable(stats)
@@ -284,36 +267,23 @@ class _BnActPatchGemm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gstats):
-        lib = _abi.load()
         z, bw, bb, stats, w = ctx.saved_tensors
         m, c = z.shape
         n, k = w.shape
         mp = m * c // k
         gy = gy.contiguous()
         dev = z.device
+        stream = _abi.raw_stream(dev)
         gw = None
         if ctx.needs_input_grad[3]:  # conv3's weight: gy^T act(bn(z)), recomputed on load
             gw = torch.empty(n, k, device=dev, dtype=torch.float32)
-            wpart = torch.empty(int(lib.gr_patch_wgrad_floats(mp, n, k)), device=dev, dtype=torch.float32)
-            rc = lib.gr_patch_wgrad_bnact(z.data_ptr(), k, gy.data_ptr(), mp, n, k, wpart.data_ptr(), gw.data_ptr(), c,
-                                          stats.data_ptr(), bw.data_ptr(), bb.data_ptr(), ctx.act, float(ctx.slope),
-                                          _stream(z))
-            if rc != 0:
-                raise RuntimeError(f"gr_patch_wgrad_bnact failed (status {rc})")
+            wpart = torch.empty(int(_abi.load().gr_patch_wgrad_floats(mp, n, k)), device=dev, dtype=torch.float32)
+            _abi.call("gr_patch_wgrad_bnact", z.data_ptr(), k, gy.data_ptr(), mp, n, k, wpart.data_ptr(), gw.data_ptr(),
+                      c, stats.data_ptr(), bw.data_ptr(), bb.data_ptr(), ctx.act, float(ctx.slope), stream)
         # the gradient of act(bn(z)) = gy w, then the BatchNorm + activation backward on z
         dblock = torch.empty(mp, k, device=dev, dtype=torch.float32)
-        rc = lib.gr_tsgemm(gy.data_ptr(), n, w.data_ptr(), 0, dblock.data_ptr(), k, mp, n, k, _stream(z))
-        if rc != 0:
-            raise RuntimeError(f"gr_tsgemm failed (status {rc})")
-        gx = torch.empty_like(z)
-        gbw = torch.empty(c, device=dev, dtype=torch.float32)
-        gbb = torch.empty(c, device=dev, dtype=torch.float32)
-        part = torch.empty(int(lib.gr_bn_scratch_doubles(m, c)), device=dev, dtype=torch.float64)
-        rc = lib.gr_bn_act_backward(z.data_ptr(), dblock.data_ptr(), m, c, bw.data_ptr(), bb.data_ptr(),
-                                    stats.data_ptr(), ctx.act, float(ctx.slope), gx.data_ptr(), gbw.data_ptr(),
-                                    gbb.data_ptr(), part.data_ptr(), _stream(z))
-        if rc != 0:
-            raise RuntimeError(f"gr_bn_act_backward failed (status {rc})")
+        _abi.call("gr_tsgemm", gy.data_ptr(), n, w.data_ptr(), 0, dblock.data_ptr(), k, mp, n, k, stream)
+        gx, gbw, gbb = _bn_act_backward(z, dblock, bw, bb, stats, ctx.act, ctx.slope)
         return gx, gbw, gbb, gw, None, None, None
 
 
@@ -385,10 +355,6 @@ def _rows_arg(rows):
     return rows.contiguous()
 
 
-def _rows_ptr(rows):
-    return rows.data_ptr() if rows is not None else None
-
-
 def _update_running(bn: nn.BatchNorm2d, stats: torch.Tensor, uses: int = 1, count_first: bool = False):
     """The running-statistics update of one training-mode forward; uses > 1 replays it as `uses` forwards of the
     same rows would, in sequence (each forward after the first counted here in num_batches_tracked, the first too
@@ -404,11 +370,9 @@ def _update_running(bn: nn.BatchNorm2d, stats: torch.Tensor, uses: int = 1, coun
         m = float(bn.momentum)
         # (through raw pointers, as F.batch_norm updates them inside its kernel: no version bump, so a torch
         # batch_norm of the same forward that saved them for its backward stays valid)
-        rc = _abi.load().gr_bn_running_update(rm.data_ptr(), rv.data_ptr(), nbt.data_ptr() if nbt is not None else None,
-                                              stats.data_ptr(), rm.numel(), float(1.0 - m), m, int(uses),
-                                              int(count) if nbt is not None else 0, _stream(stats))
-        if rc != 0:
-            raise RuntimeError(f"gr_bn_running_update failed (status {rc})")
+        _abi.call("gr_bn_running_update", rm.data_ptr(), rv.data_ptr(), nbt.data_ptr() if nbt is not None else None,
+                  stats.data_ptr(), rm.numel(), float(1.0 - m), m, int(uses), int(count) if nbt is not None else 0,
+                  _abi.raw_stream(stats.device))
         return
     for k in range(uses):
         if (k or count_first) and nbt is not None:

@@ -16,14 +16,8 @@ import math
 
 import torch
 
-
-class GrPpoLossArgs(C.Structure):
-    """Mirror of gr_ppo_loss_args (include/gr.h)."""
-    _fields_ = [("rows", C.c_int64), ("k", C.c_int32), ("clipped_value", C.c_int32), ("clip", C.c_float)] + [
-        (n, C.c_void_p) for n in ("mu", "std", "value", "act", "logp_old", "adv", "value_old", "ret", "mu_old",
-                                  "sig_old")] + [
-        (n, C.c_int64) for n in ("ld_mu", "ld_value", "ld_act", "ld_logp_old", "ld_adv", "ld_value_old", "ld_ret",
-                                 "ld_mu_old", "ld_sig_old")]
+from .. import _abi
+from .._abi import GrPpoLossArgs
 
 
 def _ld(t: torch.Tensor) -> int:
@@ -44,26 +38,16 @@ def _args(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, c
     return a
 
 
-def _call(name, *args):
-    from .. import _abi
-
-    rc = getattr(_abi.load(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed (status {rc})")
-
-
 class _PPOLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, clip, clipped_value):
-        from .. import _abi
-
         std = std.contiguous()
         a = _args(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, clip, clipped_value)
         rows = mu.shape[0]
         part = torch.empty(_abi.load().gr_ppo_loss_partials(rows), device=mu.device, dtype=torch.float32)
         sums = torch.empty(3, device=mu.device, dtype=torch.float32)
         stream = _abi.raw_stream(mu.device)
-        _call("gr_ppo_loss_forward", C.addressof(a), part.data_ptr(), sums.data_ptr(), stream)
+        _abi.call("gr_ppo_loss_forward", C.byref(a), part.data_ptr(), sums.data_ptr(), stream)
         ctx.save_for_backward(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old)
         ctx.clip, ctx.clipped_value = clip, clipped_value
         out = sums / rows  # the means (torch's mean: sum / rows)
@@ -73,8 +57,6 @@ class _PPOLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_surr, g_value, g_kl):
-        from .. import _abi
-
         mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old = ctx.saved_tensors
         a = _args(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, ctx.clip, ctx.clipped_value)
         rows, k = mu.shape
@@ -86,8 +68,8 @@ class _PPOLossFn(torch.autograd.Function):
         part = torch.empty(_abi.load().gr_ppo_loss_partials(rows), device=dev, dtype=torch.float32)
         dstd = torch.empty(k, device=dev, dtype=torch.float32)
         stream = _abi.raw_stream(dev)
-        _call("gr_ppo_loss_backward", C.addressof(a), g.data_ptr(), dmu.data_ptr(), dvalue.data_ptr(), part.data_ptr(),
-              dstd.data_ptr(), stream)
+        _abi.call("gr_ppo_loss_backward", C.byref(a), g.data_ptr(), dmu.data_ptr(), dvalue.data_ptr(), part.data_ptr(),
+                  dstd.data_ptr(), stream)
         return (dmu, dstd, dvalue.view(value.shape), None, None, None, None, None, None, None, None, None)
 
 
@@ -101,8 +83,6 @@ class _PPOLossCombinedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, clip, clipped_value,
                 value_coef, acc, kl_out, seed):
-        from .. import _abi
-
         std = std.contiguous()
         a = _args(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old, clip, clipped_value)
         rows, k = mu.shape
@@ -122,13 +102,13 @@ class _PPOLossCombinedFn(torch.autograd.Function):
             dvalue = torch.empty(rows, device=dev, dtype=torch.float32)
             dpart = torch.empty(npart, device=dev, dtype=torch.float32)
             dstd = _std_sink(std, k)
-            _call("gr_ppo_loss_forward_backward", C.addressof(a), seed.data_ptr(), C.c_float(value_coef),
-                  part.data_ptr(), sums.data_ptr(), loss.data_ptr(), stats.data_ptr(), accp, klp, dmu.data_ptr(),
-                  dvalue.data_ptr(), dpart.data_ptr(), dstd.data_ptr(), stream)
+            _abi.call("gr_ppo_loss_forward_backward", C.byref(a), seed.data_ptr(), value_coef,
+                      part.data_ptr(), sums.data_ptr(), loss.data_ptr(), stats.data_ptr(), accp, klp, dmu.data_ptr(),
+                      dvalue.data_ptr(), dpart.data_ptr(), dstd.data_ptr(), stream)
             ctx.pre = (seed.data_ptr(), dmu, dstd, dvalue.view(value.shape))
         else:
-            _call("gr_ppo_loss_forward_loss", C.addressof(a), part.data_ptr(), sums.data_ptr(), C.c_float(value_coef),
-                  loss.data_ptr(), stats.data_ptr(), accp, klp, stream)
+            _abi.call("gr_ppo_loss_forward_loss", C.byref(a), part.data_ptr(), sums.data_ptr(), value_coef,
+                      loss.data_ptr(), stats.data_ptr(), accp, klp, stream)
         ctx.save_for_backward(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old)
         ctx.clip, ctx.clipped_value, ctx.value_coef = clip, clipped_value, float(value_coef)
         ctx.mark_non_differentiable(stats)
@@ -137,8 +117,6 @@ class _PPOLossCombinedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_stats):
-        from .. import _abi
-
         if g_loss is None:
             return (None,) * 16
         if ctx.pre is not None and g_loss.data_ptr() == ctx.pre[0]:  # computed in the forward, for this seed
@@ -152,8 +130,8 @@ class _PPOLossCombinedFn(torch.autograd.Function):
         dvalue = torch.empty(rows, device=dev, dtype=torch.float32)
         part = torch.empty(_abi.load().gr_ppo_loss_partials(rows), device=dev, dtype=torch.float32)
         dstd = _std_sink(std, k)
-        _call("gr_ppo_loss_backward_loss", C.addressof(a), g.data_ptr(), C.c_float(ctx.value_coef), dmu.data_ptr(),
-              dvalue.data_ptr(), part.data_ptr(), dstd.data_ptr(), _abi.raw_stream(dev))
+        _abi.call("gr_ppo_loss_backward_loss", C.byref(a), g.data_ptr(), ctx.value_coef, dmu.data_ptr(),
+                  dvalue.data_ptr(), part.data_ptr(), dstd.data_ptr(), _abi.raw_stream(dev))
         return (dmu, dstd, dvalue.view(value.shape)) + (None,) * 13
 
 

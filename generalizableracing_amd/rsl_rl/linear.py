@@ -24,6 +24,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import _abi
+from .._abi import GrMlpArgs, GrMlpNet
+
 SPLIT = 4096  # rows per chunk (scripts/prof_update.py --split: 2048-4096 best at 65 536 and 4 096 envs)
 # set by the graph-captured PPO step (ppo.py _GraphedStep): every Linear takes _TallLinearFn, whose bias
 # gradient is gr_column_sum (see bias_grad)
@@ -44,8 +47,6 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     (1.5 ms at M = 393 216, N = 256, half of the update step)."""
     if gy.device.type != "cuda":
         return gy.float().sum(0)
-    from .. import _abi
-
     lib = _abi.load()
     gy = gy.contiguous()
     m, n = gy.shape
@@ -56,10 +57,7 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
         dtype = _abi.GR_DTYPE_F32
     part = torch.empty(lib.gr_column_sum_partials(m) * n, device=gy.device, dtype=torch.float32)
     out = torch.empty(n, device=gy.device, dtype=torch.float32)
-    rc = lib.gr_column_sum(gy.data_ptr(), dtype, m, n, part.data_ptr(), out.data_ptr(),
-                           _abi.raw_stream(gy.device))
-    if rc != 0:
-        raise RuntimeError(f"gr_column_sum failed (status {rc})")
+    _abi.call("gr_column_sum", gy.data_ptr(), dtype, m, n, part.data_ptr(), out.data_ptr(), _abi.raw_stream(gy.device))
     return out
 
 
@@ -81,8 +79,6 @@ def tall_wgrad(gy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     m, n = gy.shape
     k = x.shape[1]
     if gy.is_cuda and gy.dtype == torch.float32 and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1:
-        from .. import _abi
-
         lib = _abi.load()
         floats = int(lib.gr_patch_wgrad_floats(m, n, k))
         if floats > 0:
@@ -91,10 +87,8 @@ def tall_wgrad(gy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
                 gy = gy.clone()     # offset is re-based, not sent to the fallback or rejected)
             gw = torch.empty(n, k, device=gy.device, dtype=torch.float32)
             part = torch.empty(floats, device=gy.device, dtype=torch.float32)
-            rc = lib.gr_patch_wgrad(x.data_ptr(), x.stride(0), gy.data_ptr(), m, n, k, part.data_ptr(), gw.data_ptr(),
-                                    _abi.raw_stream(gy.device))
-            if rc != 0:
-                raise RuntimeError(f"gr_patch_wgrad failed (status {rc})")
+            _abi.call("gr_patch_wgrad", x.data_ptr(), x.stride(0), gy.data_ptr(), m, n, k, part.data_ptr(),
+                      gw.data_ptr(), _abi.raw_stream(gy.device))
             return gw
     return split_k_wgrad(gy, x)
 
@@ -146,31 +140,15 @@ HEAD_MAX_IN = 256     # gr_head_* / gr_mlp_in_*: hidden features (a multiple of 
 IN_MAX = 32           # gr_mlp_in_*: input features (a multiple of 4)
 
 
-def _lib_call(name, *args):
-    from .. import _abi
-
-    rc = getattr(_abi.load(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed (status {rc})")
-
-
-def _stream(t):
-    from .. import _abi
-
-    return _abi.raw_stream(t.device)
-
-
 def _head_backward(z, gy, w, slope):
     """gr_head_backward -> (gz, gW, gb, column sums of gz)."""
-    from .. import _abi
-
     m, h = z.shape
     k = w.shape[0]
     gz = torch.empty_like(z)
     part = torch.empty(_abi.load().gr_head_partials(m, k, h), device=z.device, dtype=torch.float32)
     sums = torch.empty(k * h + k + h, device=z.device, dtype=torch.float32)
-    _lib_call("gr_head_backward", z.data_ptr(), gy.data_ptr(), m, h, w.data_ptr(), k, float(slope), gz.data_ptr(),
-              part.data_ptr(), sums.data_ptr(), _stream(z))
+    _abi.call("gr_head_backward", z.data_ptr(), gy.data_ptr(), m, h, w.data_ptr(), k, float(slope), gz.data_ptr(),
+              part.data_ptr(), sums.data_ptr(), _abi.raw_stream(z.device))
     return gz, sums[:k * h].view(k, h), sums[k * h:k * h + k], sums[k * h + k:]
 
 
@@ -178,8 +156,8 @@ def _head_forward(z, w, b, slope):
     m, h = z.shape
     k = w.shape[0]
     y = torch.empty(m, k, device=z.device, dtype=torch.float32)
-    _lib_call("gr_head_forward", z.data_ptr(), m, h, w.data_ptr(), b.data_ptr(), k, float(slope), y.data_ptr(),
-              _stream(z))
+    _abi.call("gr_head_forward", z.data_ptr(), m, h, w.data_ptr(), b.data_ptr(), k, float(slope), y.data_ptr(),
+              _abi.raw_stream(z.device))
     return y
 
 
@@ -225,8 +203,8 @@ class _LeakyMLPFn(torch.autograd.Function):
         m, d = x.shape
         h1n = w1.shape[0]
         h1 = torch.empty(m, h1n, device=x.device, dtype=torch.float32)
-        _lib_call("gr_mlp_in_forward", x.data_ptr(), m, d, x.stride(0), w1.data_ptr(), b1.data_ptr(), h1n,
-                  float(slope), h1.data_ptr(), _stream(x))
+        _abi.call("gr_mlp_in_forward", x.data_ptr(), m, d, x.stride(0), w1.data_ptr(), b1.data_ptr(), h1n,
+                  float(slope), h1.data_ptr(), _abi.raw_stream(x.device))
         z2 = F.linear(h1, w2, b2)
         y = _head_forward(z2, w3.contiguous(), b3, slope)
         ctx.save_for_backward(x, h1, z2, w2, w3)
@@ -235,8 +213,6 @@ class _LeakyMLPFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .. import _abi
-
         x, h1, z2, w2, w3 = ctx.saved_tensors
         gz2, gw3, gb3, gb2 = _head_backward(z2, gy.contiguous().float(), w3.contiguous(), ctx.slope)
         gh1 = gz2 @ w2
@@ -245,8 +221,8 @@ class _LeakyMLPFn(torch.autograd.Function):
         h1n = h1.shape[1]
         part = torch.empty(_abi.load().gr_mlp_in_partials(m, d, h1n), device=x.device, dtype=torch.float32)
         sums = torch.empty(h1n * d + h1n, device=x.device, dtype=torch.float32)
-        _lib_call("gr_mlp_in_backward", gh1.data_ptr(), h1.data_ptr(), x.data_ptr(), m, d, x.stride(0), h1n,
-                  ctx.slope, part.data_ptr(), sums.data_ptr(), _stream(x))
+        _abi.call("gr_mlp_in_backward", gh1.data_ptr(), h1.data_ptr(), x.data_ptr(), m, d, x.stride(0), h1n,
+                  ctx.slope, part.data_ptr(), sums.data_ptr(), _abi.raw_stream(x.device))
         return None, sums[:h1n * d].view(h1n, d), sums[h1n * d:], gw2, gb2, gw3, gb3, None
 
 
@@ -308,19 +284,6 @@ class MLP(nn.Sequential):
 
 
 # ------------------------------------------------------------------------------ whole-network MFMA kernels (round 4)
-class GrMlpNet(C.Structure):
-    """Mirror of gr_mlp_net (include/gr.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "w3", "b3", "h1", "z2", "y", "gy", "gz2",
-                                          "grads")] + [("ldx", C.c_int64), ("d", C.c_int32), ("k", C.c_int32),
-                                                       ("h1mask", C.c_void_p)]
-
-
-class GrMlpArgs(C.Structure):
-    """Mirror of gr_mlp_args (include/gr.h)."""
-    _fields_ = [("net", GrMlpNet * 2), ("rows", C.c_int64), ("nets", C.c_int32), ("hidden", C.c_int32),
-                ("slope", C.c_float), ("reserved", C.c_int32), ("partial", C.c_void_p)]
-
-
 def _mlp_layers(mlp: nn.Module):
     """(l1, l2, l3, slope) of a Linear -> LeakyReLU -> Linear -> LeakyReLU -> Linear stack, else None."""
     mods = list(mlp) if isinstance(mlp, nn.Sequential) else []
@@ -394,15 +357,13 @@ class _FusedMLPsFn(torch.autograd.Function):
             a.hidden = h
             keep += [h1, z2, mask]
             outs.append(y)
-        _lib_call("gr_mlp_forward", C.byref(a), _stream(xs[0]))
+        _abi.call("gr_mlp_forward", C.byref(a), _abi.raw_stream(xs[0].device))
         ctx.nnets, ctx.slope = nnets, float(slope)
         ctx.save_for_backward(*xs, *keep, *params)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gys):
-        from .. import _abi
-
         nnets = ctx.nnets
         saved = ctx.saved_tensors
         xs, keep, params = saved[:nnets], saved[nnets:4 * nnets], saved[4 * nnets:]
@@ -444,7 +405,7 @@ class _FusedMLPsFn(torch.autograd.Function):
             grads_out += split
         part = torch.empty(_abi.load().gr_mlp_partials(rows, a.hidden, nnets), device=dev, dtype=torch.float32)
         a.partial = part.data_ptr()
-        _lib_call("gr_mlp_backward", C.byref(a), _stream(xs[0]))
+        _abi.call("gr_mlp_backward", C.byref(a), _abi.raw_stream(xs[0].device))
         return (None, None) + (None,) * nnets + tuple(grads_out)
 
 
@@ -458,8 +419,6 @@ def _mask_words(rows: int, hidden: int) -> int:
     """gr_mlp_h1mask_words for H = 256 (mlp_bwd256h); 0 (no mask: the backward reads h1) for H = 128."""
     if hidden != 256 or not _H1_MASKS:
         return 0
-    from .. import _abi
-
     return int(_abi.load().gr_mlp_h1mask_words(rows, hidden))
 
 

@@ -9,13 +9,12 @@ applies the identical update.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.optim as optim
 import torch.distributed as dist
 
+from .. import _abi
 from . import distributed as gdist
 from . import flat_adam as _fadam
 from . import fused_loss as _floss
@@ -435,8 +434,8 @@ class _GraphedStep:
             return
         if self._adaptive():  # on the rank-averaged KL mean once the flat buffer has been all-reduced: the
             # comparisons of ppo.py:133-150 on the device, one launch (gr_adaptive_lr)
-            _lin._lib_call("gr_adaptive_lr", self.flat.extra.data_ptr(), self.lr.data_ptr(),
-                           C.c_double(alg.desired_kl), C.c_double(1e-5), C.c_double(1e-2), _lin._stream(self.lr))
+            _abi.call("gr_adaptive_lr", self.flat.extra.data_ptr(), self.lr.data_ptr(), alg.desired_kl, 1e-5, 1e-2,
+                      _abi.raw_stream(self.lr.device))
         _fadam.clip_grad_norm_(self.opt, self.params, alg.max_grad_norm)
         self.opt.step()
 

@@ -28,6 +28,7 @@ import math
 import torch
 import torch.nn as nn
 
+from .. import _abi
 from . import distributed as gdist
 from . import flat_adam as _fadam
 from . import fused_loss as _floss
@@ -47,14 +48,10 @@ def _mix(obs, next_obs, w):
              and obs.is_contiguous() and next_obs.is_contiguous()
              and not (obs.requires_grad or next_obs.requires_grad or w.requires_grad))
     if fused:
-        from .. import _abi
-
         w = w.reshape(-1).float().contiguous()
         out = torch.empty_like(obs)
-        rc = _abi.load().gr_l2c2_mix(obs.data_ptr(), next_obs.data_ptr(), w.data_ptr(), obs.shape[0], obs.shape[1],
-                                     out.data_ptr(), _abi.raw_stream(obs.device))
-        if rc != 0:
-            raise RuntimeError(f"gr_l2c2_mix failed (status {rc})")
+        _abi.call("gr_l2c2_mix", obs.data_ptr(), next_obs.data_ptr(), w.data_ptr(), obs.shape[0], obs.shape[1],
+                  out.data_ptr(), _abi.raw_stream(obs.device))
         return out
     return obs + w * (next_obs - obs)
 
@@ -62,15 +59,11 @@ def _mix(obs, next_obs, w):
 def _mix_rows(src, rows_obs, rows_next, w):
     """_mix(src[rows_obs], src[rows_next], w) in one pass over the storage rows (gr_l2c2_mix_rows): no gathered copies
     of the pair."""
-    from .. import _abi
-
     w = w.reshape(-1).float().contiguous()
     out = torch.empty(rows_obs.numel(), src.shape[1], device=src.device, dtype=torch.float32)
-    rc = _abi.load().gr_l2c2_mix_rows(src.data_ptr(), src.data_ptr(), src.stride(0), rows_obs.data_ptr(),
-                                      rows_next.data_ptr(), w.data_ptr(), out.shape[0], out.shape[1], out.data_ptr(),
-                                      _abi.raw_stream(src.device))
-    if rc != 0:
-        raise RuntimeError(f"gr_l2c2_mix_rows failed (status {rc})")
+    _abi.call("gr_l2c2_mix_rows", src.data_ptr(), src.data_ptr(), src.stride(0), rows_obs.data_ptr(),
+              rows_next.data_ptr(), w.data_ptr(), out.shape[0], out.shape[1], out.data_ptr(),
+              _abi.raw_stream(src.device))
     return out
 
 

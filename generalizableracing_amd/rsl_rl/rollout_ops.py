@@ -16,32 +16,11 @@ import ctypes as C
 
 import torch
 
-
-class GrTransitionArgs(C.Structure):
-    """Mirror of gr_transition_args (include/gr.h)."""
-    _fields_ = [("n", C.c_int64), ("k", C.c_int32), ("dones_bytes", C.c_int32), ("gamma", C.c_float),
-                ("pad", C.c_int32)] + [
-        (f, C.c_void_p) for f in ("reward", "dones", "time_out", "value", "action", "logp", "mu", "sigma")] + [
-        (f, C.c_int64) for f in ("ld_value", "ld_action", "ld_logp", "ld_mu", "ld_sigma")] + [
-        (f, C.c_void_p) for f in ("out_reward", "out_dones", "out_action", "out_value", "out_logp", "out_mu",
-                                  "out_sigma")]
+from .. import _abi
+from .._abi import GrTransitionArgs
 
 
 _FLAG_BYTES = {torch.bool: 1, torch.uint8: 1, torch.int32: 4, torch.int64: 8}
-
-
-def _call(name, *args):
-    from .. import _abi
-
-    rc = getattr(_abi.load(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed (status {rc})")
-
-
-def _stream(t):
-    from .. import _abi
-
-    return _abi.raw_stream(t.device)
 
 
 def _flags_ok(t, n) -> bool:
@@ -105,7 +84,7 @@ def store_transition(storage, tr, rewards, dones, time_outs, gamma):
                       ("out_value", st.values), ("out_logp", st.actions_log_prob), ("out_mu", st.mu),
                       ("out_sigma", st.sigma)):
         setattr(a, name, dst[t].data_ptr())
-    _call("gr_store_transition", C.addressof(a), _stream(rewards))
+    _abi.call("gr_store_transition", C.byref(a), _abi.raw_stream(rewards.device))
     st.step += 1
 
 
@@ -121,9 +100,9 @@ def gae_ok(storage, last_values) -> bool:
 def gae(storage, last_values, gamma, lam):
     """compute_returns' backward loop + advantages = returns - values, one launch."""
     st = storage
-    _call("gr_gae", st.num_envs, st.num_transitions_per_env, C.c_float(gamma), C.c_float(lam),
-          st.rewards.data_ptr(), st.dones.data_ptr(), st.values.data_ptr(), last_values.data_ptr(),
-          _ld(last_values), st.returns.data_ptr(), st.advantages.data_ptr(), _stream(st.rewards))
+    _abi.call("gr_gae", st.num_envs, st.num_transitions_per_env, gamma, lam,
+              st.rewards.data_ptr(), st.dones.data_ptr(), st.values.data_ptr(), last_values.data_ptr(),
+              _ld(last_values), st.returns.data_ptr(), st.advantages.data_ptr(), _abi.raw_stream(st.rewards.device))
 
 
 class EpisodeStats:
@@ -152,9 +131,9 @@ class EpisodeStats:
         r = rewards.reshape(-1)
         if (self.cur_rew.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == self.n
                 and _flags_ok(dones, self.n)):
-            _call("gr_episode_accumulate", self.n, r.data_ptr(), dones.data_ptr(), _FLAG_BYTES[dones.dtype],
-                  self.cur_rew.data_ptr(), self.cur_len.data_ptr(), self.fin_rew[t].data_ptr(),
-                  self.fin_len[t].data_ptr(), self.fin_done[t].data_ptr(), _stream(self.cur_rew))
+            _abi.call("gr_episode_accumulate", self.n, r.data_ptr(), dones.data_ptr(), _FLAG_BYTES[dones.dtype],
+                      self.cur_rew.data_ptr(), self.cur_len.data_ptr(), self.fin_rew[t].data_ptr(),
+                      self.fin_len[t].data_ptr(), self.fin_done[t].data_ptr(), _abi.raw_stream(self.cur_rew.device))
         else:
             d = dones.reshape(-1) > 0
             self.cur_rew += r

@@ -23,10 +23,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import _abi
 from . import linear as _lin
 from .actor_critic import ActorCritic, resolve_nn_activation
-from .fused_bn import (batch_norm_act, bn_act_conv, bn_act_conv_applicable, fused_applicable, stem1_applicable,
-                       stem1_bn_act, stem12_applicable, stem12_bn_act_conv)
+from .fused_bn import (_update_running, batch_norm_act, bn_act_conv, bn_act_conv_applicable, bn_stats, fused_applicable,
+                       stem1_applicable, stem1_bn_act, stem12_applicable, stem12_bn_act_conv)
 
 
 def _conv_out(n: int, k: int, s: int) -> int:
@@ -83,8 +84,6 @@ def _tsgemm(a, w, b_nk: bool):
     else None."""
     if not (a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1):
         return None
-    from .. import _abi
-
     k = a.shape[1]
     n = w.shape[0] if b_nk else w.shape[1]
     if not ((k == 128 and n == 64 and b_nk) or (k == 64 and n == 128 and not b_nk)
@@ -92,17 +91,13 @@ def _tsgemm(a, w, b_nk: bool):
         return None
     w = w.contiguous()
     out = torch.empty(a.shape[0], n, device=a.device, dtype=torch.float32)
-    rc = _abi.load().gr_tsgemm(a.data_ptr(), a.stride(0), w.data_ptr(), int(b_nk), out.data_ptr(), n, a.shape[0], k,
-                               n, _abi.raw_stream(a.device))
-    if rc != 0:
-        raise RuntimeError(f"gr_tsgemm failed (status {rc})")
+    _abi.call("gr_tsgemm", a.data_ptr(), a.stride(0), w.data_ptr(), int(b_nk), out.data_ptr(), n, a.shape[0], k, n,
+              _abi.raw_stream(a.device))
     return out
 
 
 def _abi_wgrad_ok(gy, x) -> bool:
     """gr_patch_wgrad covers the shape (conv3: 64 x 128, the final Linear: 192 x 1280, conv2: 32 x 144)."""
-    from .. import _abi
-
     return (gy.dtype == torch.float32 and x.dtype == torch.float32 and x.stride(-1) == 1
             and int(_abi.load().gr_patch_wgrad_floats(x.shape[0], gy.shape[1], x.shape[1])) > 0)
 
@@ -176,8 +171,6 @@ class VisionActorCritic(ActorCritic):
         """nn.BatchNorm2d.forward on channels-last rows [M, C] (M = batch*height*width)."""
         y = self._bn_once(bn, x)
         if self._bn_uses > 1 and bn.training and bn.track_running_stats and bn.running_mean is not None:
-            from .fused_bn import _update_running
-
             with torch.no_grad():
                 xd = x.detach().double()
                 stats = torch.stack([xd.mean(0), xd.var(0, unbiased=False), xd.var(0, unbiased=False),
@@ -217,17 +210,7 @@ class VisionActorCritic(ActorCritic):
             return
         if x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() \
                 and x.shape[1] in (4, 8, 16, 32, 64) and x.shape[0] >= 2 and self.fused_bn:
-            from .. import _abi
-            from .fused_bn import _stream, _update_running
-
-            lib = _abi.load()
-            m, c = x.shape
-            stats = torch.empty(4, c, device=x.device, dtype=torch.float32)
-            part = torch.empty(int(lib.gr_bn_scratch_doubles(m, c)), device=x.device, dtype=torch.float64)
-            rc = lib.gr_bn_stats(x.data_ptr(), m, c, float(bn.eps), stats.data_ptr(), part.data_ptr(), _stream(x))
-            if rc != 0:
-                raise RuntimeError(f"gr_bn_stats failed (status {rc})")
-            _update_running(bn, stats, self._bn_uses, count_first=True)
+            _update_running(bn, bn_stats(x, bn.eps), self._bn_uses, count_first=True)
             return
         self._bn(bn, x.detach())
 

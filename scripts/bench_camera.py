@@ -61,7 +61,7 @@ def run(n=65536, steps=40, warmup=6, no_noise=False, period=None, device="cuda:0
     t0 = time.perf_counter()
     for k in range(args.steps):
         env._advance()
-        env._call("gr_step", acts[k % 8].data_ptr(), env._stream())
+        env._call("gr_step", acts[k % 8].data_ptr(), _abi.raw_stream(env.device))
         ev[k][0].record()
         env._render(_abi.GR_CAM_STEP)
         ev[k][1].record()

@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from generalizableracing_amd import _abi  # noqa: E402
 
 
 def main():
@@ -30,7 +31,7 @@ def main():
     ev = torch.cuda.Event()
     modes = ["sync", "spin_then_sync", "eager_env", "eager_raw"]
     res = {m: [] for m in modes}
-    stream = env._stream()
+    stream = _abi.raw_stream(env.device)
     ptrs = [actions[k].data_ptr() for k in range(bench.ACTION_RING)]
     lib, ctx = env._lib, env._ctx
     for r in range(len(modes) * a.reps):

@@ -7,7 +7,8 @@ from collections import deque
 import numpy as np
 import torch
 
-from generalizableracing_amd.rsl_rl.rollout_ops import EpisodeStats, GrTransitionArgs
+from generalizableracing_amd._abi import GrTransitionArgs
+from generalizableracing_amd.rsl_rl.rollout_ops import EpisodeStats
 
 
 def _reference_deques(rews, dones, maxlen=100):
