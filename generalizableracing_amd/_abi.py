@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 6
+GR_ABI_VERSION = 7
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -351,6 +351,10 @@ SIGNATURES = {
     "gr_mlp_forward": (C.c_int, [C.POINTER(GrMlpArgs), vp]),
     "gr_mlp_backward": (C.c_int, [C.POINTER(GrMlpArgs), vp]),
     "gr_mlp_args_size": (C.c_size_t, []),
+    "gr_lcp_scratch_floats": (i64, [i64, i32]),
+    # (mu, ld, act, ld, std, h1, z2, w1, w2, w3, rows, H, d, k, slope, ...)
+    "gr_lcp_forward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 6),
+    "gr_lcp_backward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 10),
     "gr_bn_scratch_doubles": (i64, [i64, i32]),
     "gr_bn_act_forward": (C.c_int, [vp, i64, i32, vp, vp, f32, i32, f32, vp, vp, vp, vp]),
     "gr_bn_act_backward": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp]),

@@ -1237,6 +1237,55 @@ int gr_mlp_backward(const gr_mlp_args* a, void* stream) {
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
+int64_t gr_lcp_scratch_floats(int64_t rows, int32_t hidden) {
+  if (rows < 0 || (hidden != 128 && hidden != 256)) return GR_ERR_ARG;
+  return gr::lcp_scratch_floats(rows, hidden);
+}
+
+// shapes, the 32-bit offset limit and alignment of the arguments gr_lcp_forward and gr_lcp_backward share
+static bool lcp_args_ok(const float* mu, int64_t ld_mu, const float* act, int64_t ld_act, const float* std,
+                        const float* h1, const float* z2, const float* w1, const float* w2, const float* w3,
+                        int64_t rows, int32_t hidden, int32_t d, int32_t k, const float* g, const float* v1,
+                        const float* v2, const float* scratch) {
+  if (rows <= 0 || (hidden != 128 && hidden != 256) || d < 4 || d > 32 || d % 4 || k < 1 || k > 4 || ld_mu < k ||
+      ld_act < k)
+    return false;
+  // the kernels index rows and element offsets in 32 bits (gr_lcp.hip): rows * max(H, ld_mu, ld_act) < 2^31
+  int64_t w = hidden;
+  w = ld_mu > w ? ld_mu : w;
+  w = ld_act > w ? ld_act : w;
+  if (rows > (int64_t)GR_MLP_MAX_ELEMS / w) return false;
+  return mu && act && std && h1 && z2 && w1 && w2 && w3 && g && v1 && v2 && scratch && aligned16(h1) &&
+         aligned16(z2) && aligned16(w1) && aligned16(w2) && aligned16(w3) && aligned16(g) && aligned16(v1) &&
+         aligned16(v2) && aligned16(scratch);
+}
+
+int gr_lcp_forward(const float* mu, int64_t ld_mu, const float* act, int64_t ld_act, const float* std,
+                   const float* h1, const float* z2, const float* w1, const float* w2, const float* w3, int64_t rows,
+                   int32_t hidden, int32_t d, int32_t k, float slope, float* g, float* v1, float* v2, float* scratch,
+                   float* penalty, void* stream) {
+  if (!lcp_args_ok(mu, ld_mu, act, ld_act, std, h1, z2, w1, w2, w3, rows, hidden, d, k, g, v1, v2, scratch) ||
+      !penalty)
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_lcp_forward(mu, ld_mu, act, ld_act, std, h1, z2, w1, w2, w3, rows, hidden, d, k,
+                                              slope, g, v1, v2, scratch, penalty, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+int gr_lcp_backward(const float* mu, int64_t ld_mu, const float* act, int64_t ld_act, const float* std,
+                    const float* h1, const float* z2, const float* w1, const float* w2, const float* w3, int64_t rows,
+                    int32_t hidden, int32_t d, int32_t k, float slope, const float* g, const float* v1,
+                    const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
+                    float* grads, void* stream) {
+  if (!lcp_args_ok(mu, ld_mu, act, ld_act, std, h1, z2, w1, w2, w3, rows, hidden, d, k, g, v1, v2, scratch) ||
+      !g_pen || !s1 || !aligned16(s1) || !dmu || !dstd || !grads)
+    return GR_ERR_ARG;
+  const hipError_t e =
+      gr::launch_lcp_backward(mu, ld_mu, act, ld_act, std, h1, z2, w1, w2, w3, rows, hidden, d, k, slope, g, v1, v2,
+                              g_pen, s1, scratch, dmu, dstd, grads, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
 int gr_adam_prepare(gr_adam_segment* t, int32_t nseg, int32_t* nblocks) {
   if (!t || !nblocks || nseg < 1 || nseg > GR_ADAM_MAX_SEGMENTS) return GR_ERR_ARG;
   int64_t nb = 0;

@@ -208,6 +208,19 @@ hipError_t launch_terrain_commit(const TerrainCommitArgs& a, hipStream_t s);
 hipError_t launch_mlp_forward(const gr_mlp_args& a, hipStream_t s);
 hipError_t launch_mlp_backward(const gr_mlp_args& a, hipStream_t s);
 int64_t mlp_partial_floats(long long rows, int hidden, int nets, int max_d, int max_k);
+int mlp_wgrad_splits(long long rows, int hidden, int nets);
+hipError_t launch_mlp_wgrad(const gr_mlp_args& a, float* wpart, hipStream_t s);
+// gr_lcp.hip: PPOLCP's gradient penalty and its gradient over the actor
+int64_t lcp_scratch_floats(long long rows, int hidden);
+hipError_t launch_lcp_forward(const float* mu, long long ld_mu, const float* act, long long ld_act, const float* std,
+                              const float* h1, const float* z2, const float* w1, const float* w2, const float* w3,
+                              long long rows, int hidden, int d, int k, float slope, float* g, float* v1, float* v2,
+                              float* scratch, float* penalty, hipStream_t s);
+hipError_t launch_lcp_backward(const float* mu, long long ld_mu, const float* act, long long ld_act, const float* std,
+                               const float* h1, const float* z2, const float* w1, const float* w2, const float* w3,
+                               long long rows, int hidden, int d, int k, float slope, const float* g, const float* v1,
+                               const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
+                               float* grads, hipStream_t s);
 hipError_t launch_in_backward(const float* gh, const float* hv, const float* x, long long m, int d, int ldx, int h,
                               float slope, float* part, float* sums, hipStream_t s);
 // Camera launch (camera_kernel, gr_camera.hip).  Dynamic LDS: the normal table and the ray tables (workgroup), then

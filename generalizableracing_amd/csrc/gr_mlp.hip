@@ -1304,6 +1304,16 @@ static hipError_t launch_wgrad_t(const gr_mlp_args& a, int splits, long long rps
   return hipGetLastError();
 }
 
+// mlp_wgrad on its own (gr_lcp.hip: gW2 = v2^T s1 with (gz2, h1) := (v2, s1)): wpart holds
+// a.nets * mlp_wgrad_splits(...) * H * H floats, part[net][split][H][H]
+int mlp_wgrad_splits(long long rows, int hidden, int nets) { return mlp_splits(rows, hidden, nets); }
+
+hipError_t launch_mlp_wgrad(const gr_mlp_args& a, float* wpart, hipStream_t s) {
+  const int splits = mlp_splits(a.rows, a.hidden, a.nets);
+  const long long rps = mlp_rows_per_split(a.rows, splits);
+  return a.hidden == 256 ? launch_wgrad_t<256>(a, splits, rps, wpart, s) : launch_wgrad_t<128>(a, splits, rps, wpart, s);
+}
+
 hipError_t launch_mlp_backward(const gr_mlp_args& a, hipStream_t s) {
   int d = a.net[0].d, k = a.net[0].k;
   if (a.nets > 1) {

@@ -6,5 +6,7 @@ from .on_policy_runner import OnPolicyRunner  # noqa: F401
 from .ppo import PPO  # noqa: F401
 from .rollout_storage import RolloutStorage  # noqa: F401
 from .ppo_l2c2 import PPOL2C2  # noqa: F401
+from .ppo_lcp import PPOLCP  # noqa: F401
+from .config import QuadcopterLCPPPORunnerCfg, RslRlPpoLcpAlgorithmCfg  # noqa: F401
 from .rollout_storage_l2c2 import RolloutStorageL2C2  # noqa: F401
 from .vision_actor_critic import VisionActorCritic  # noqa: F401

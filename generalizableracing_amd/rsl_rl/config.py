@@ -99,6 +99,24 @@ class QuadcopterL2C2PPORunnerCfg(QuadcopterPPORunnerCfg):
 
 
 @dataclass
+class RslRlPpoLcpAlgorithmCfg(RslRlPpoAlgorithmCfg):
+    """PPOLCP (standalone/rsl_rl/ext/algorithms/ppo_lcp.py): PPO plus the Lipschitz gradient penalty on the actor.
+    The schedule [start coef, end coef, first update of the ramp, updates of the ramp] is the one the racing recipe
+    leaves commented out (rsl_rl_ppo_cfg.py:102)."""
+
+    class_name: str = "PPOLCP"
+    grad_penalty_coef_schedule: list = field(default_factory=lambda: [0.1, 0.1, 700, 1000])
+
+
+@dataclass
+class QuadcopterLCPPPORunnerCfg(QuadcopterPPORunnerCfg):
+    """PPOLCP on the state-only MLP policy."""
+
+    experiment_name: str = "racing_ppo_lcp"
+    algorithm: RslRlPpoAlgorithmCfg = field(default_factory=RslRlPpoLcpAlgorithmCfg)
+
+
+@dataclass
 class RslRlPpoVisionActorCriticCfg(RslRlPpoActorCriticCfg):
     """rsl_rl_ppo_cfg.py:43-52."""
 

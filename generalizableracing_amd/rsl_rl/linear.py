@@ -329,10 +329,11 @@ class _FusedMLPsFn(torch.autograd.Function):
     """Up to two MLPs (the actor and the critic) on their input rows, forward and backward each as one set of
     whole-network fp32-MFMA launches for both networks (gr_mlp_forward / gr_mlp_backward, gr_mlp.hip).  Forward
     saves h1 and z2 per network; the backward returns every parameter gradient from one fixed-order reduction and
-    leaves the saved tensors intact (a retained graph may run it again)."""
+    leaves the saved tensors intact (a retained graph may run it again).  extras: the first network's saved h1 and z2
+    follow the outputs, non-differentiable (fused_lcp.py reads their signs)."""
 
     @staticmethod
-    def forward(ctx, nnets, slope, *args):
+    def forward(ctx, nnets, slope, extras, *args):
         xs, params = args[:nnets], args[nnets:]
         rows = xs[0].shape[0]
         dev = xs[0].device
@@ -360,6 +361,9 @@ class _FusedMLPsFn(torch.autograd.Function):
         _abi.call("gr_mlp_forward", C.byref(a), _abi.raw_stream(xs[0].device))
         ctx.nnets, ctx.slope = nnets, float(slope)
         ctx.save_for_backward(*xs, *keep, *params)
+        if extras:
+            ctx.mark_non_differentiable(keep[0], keep[1])
+            return tuple(outs) + (keep[0], keep[1])
         return tuple(outs)
 
     @staticmethod
@@ -406,7 +410,7 @@ class _FusedMLPsFn(torch.autograd.Function):
         part = torch.empty(_abi.load().gr_mlp_partials(rows, a.hidden, nnets), device=dev, dtype=torch.float32)
         a.partial = part.data_ptr()
         _abi.call("gr_mlp_backward", C.byref(a), _abi.raw_stream(xs[0].device))
-        return (None, None) + (None,) * nnets + tuple(grads_out)
+        return (None, None, None) + (None,) * nnets + tuple(grads_out)
 
 
 # True: the forward also writes the sign of h1 as bits and the backward (H = 256) reads those instead of the h1 rows
@@ -439,10 +443,11 @@ def _sink_region(params):
     return torch.as_strided(base, (off,), (1,), base.storage_offset())
 
 
-def fused_mlps(nets, xs):
-    """The outputs of `nets` (nn.Sequential MLPs) on `xs` through _FusedMLPsFn; call only when networks_fusable."""
+def fused_mlps(nets, xs, extras=False):
+    """The outputs of `nets` (nn.Sequential MLPs) on `xs` through _FusedMLPsFn; call only when networks_fusable.
+    extras: followed by the first network's saved h1 = lrelu(z1) and z2 [rows, H], non-differentiable."""
     params, slope = [], None
     for net in nets:
         l1, l2, l3, slope = _mlp_layers(net)
         params += [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
-    return _FusedMLPsFn.apply(len(nets), slope, *xs, *params)
+    return _FusedMLPsFn.apply(len(nets), slope, bool(extras), *xs, *params)

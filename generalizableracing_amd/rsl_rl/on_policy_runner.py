@@ -21,10 +21,11 @@ from . import distributed as gdist
 from .actor_critic import ActorCritic, EmpiricalNormalization
 from .ppo import PPO
 from .ppo_l2c2 import PPOL2C2
+from .ppo_lcp import PPOLCP
 from .rollout_ops import EpisodeStats
 from .vision_actor_critic import VisionActorCritic
 
-ALGORITHMS = {"PPO": PPO, "PPOL2C2": PPOL2C2}
+ALGORITHMS = {"PPO": PPO, "PPOL2C2": PPOL2C2, "PPOLCP": PPOLCP}
 POLICIES = {"ActorCritic": ActorCritic, "VisionActorCritic": VisionActorCritic}
 
 

@@ -38,8 +38,8 @@ extern "C" {
 /* 2: GR_NUM_PLANES 17 (obstacle hint, rotor constants), gr_policy_args.precision, the observation sink and the
  * status word; gr_policy_args_size.  3: gr_stem1_* y_rows / gy_rows.  4: the gr_stem1_* / gr_stem12_* row indices
  * (`rows` after `off`).  5: gr_stem12_backward_w2 (conv2's weight gradient inside the first block's backward).
- * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments` */
-#define GR_ABI_VERSION 6
+ * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward */
+#define GR_ABI_VERSION 7
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -633,6 +633,31 @@ int64_t gr_mlp_partials(int64_t rows, int32_t hidden, int32_t nets);
 int gr_mlp_forward(const gr_mlp_args* args, void* stream);
 int gr_mlp_backward(const gr_mlp_args* args, void* stream);
 size_t gr_mlp_args_size(void);
+
+/* PPOLCP's Lipschitz gradient penalty on the actor and its gradient (standalone/rsl_rl/ext/algorithms/ppo_lcp.py:
+ * 105-108: P = mean_rows |d sum(log pi(a|x)) / dx|^2, there through torch's double backward).  LeakyReLU's second
+ * derivative is zero, so with D = (z > 0 ? 1 : slope) from the sign of gr_mlp_forward's saved h1 and z2:
+ *   gr_lcp_forward : delta = (act - mu) / std^2;  v2 = D2 (W3^T delta);  v1 = D1 (W2^T v2);  g = W1^T v1;
+ *                    penalty[0] = mean_rows |g|^2.  Out: g [rows][d], v1, v2 [rows][H], penalty [1].
+ *   gr_lcp_backward: g_pen [1] = dloss/dpenalty (a device scalar); gb = (2 g_pen / rows) g;  s1 = D1 (W1 gb);
+ *                    s2 = D2 (W2 s1);  dbar = W3 s2.  Out: dmu [rows][k] = -dbar / std^2, dstd [k] =
+ *                    sum_rows -2 delta dbar / std, grads = [gW1 (H d) | gW2 (H H) | gW3 (k H)] = [v1^T gb |
+ *                    v2^T s1 | delta^T s2] (no bias term); s1 [rows][H] is caller-owned scratch.
+ * mu and act are row-strided (ld_* floats, first k columns); the rest as gr_mlp_*: H = 128 or 256, d <= 32 (a
+ * multiple of 4), k <= 4, row-major fp32, 16-byte aligned matrices, the H x H products on v_mfma_f32_16x16x4_f32.
+ * Context-free, on `stream`, graph-capturable, no atomics, fixed summation order (bit-reproducible); `scratch` is
+ * caller-owned, gr_lcp_scratch_floats(rows, H) floats (either call).
+ * Size limit: rows * max(H, ld_mu, ld_act) < GR_MLP_MAX_ELEMS (32-bit offsets), else GR_ERR_ARG. */
+int64_t gr_lcp_scratch_floats(int64_t rows, int32_t hidden);
+int gr_lcp_forward(const float* mu, int64_t ld_mu, const float* act, int64_t ld_act, const float* std,
+                   const float* h1, const float* z2, const float* w1, const float* w2, const float* w3, int64_t rows,
+                   int32_t hidden, int32_t d, int32_t k, float slope, float* g, float* v1, float* v2, float* scratch,
+                   float* penalty, void* stream);
+int gr_lcp_backward(const float* mu, int64_t ld_mu, const float* act, int64_t ld_act, const float* std,
+                    const float* h1, const float* z2, const float* w1, const float* w2, const float* w3, int64_t rows,
+                    int32_t hidden, int32_t d, int32_t k, float slope, const float* g, const float* v1,
+                    const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
+                    float* grads, void* stream);
 
 /* The PPO losses of one mini-batch, forward and backward (standalone/rsl_rl/ext/algorithms/ppo.py:133-169: the
  * adaptive-rate KL, the clipped surrogate, the (clipped) value loss; the Gaussian log prob of rsl_rl's

@@ -43,7 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device", type=str, default=None, help="cuda:N (default: cuda:LOCAL_RANK)")
     p.add_argument("--log_root", type=str, default="logs", help="Root of logs/rsl_rl/<experiment>.")
     p.add_argument("--agent", type=str, default="rsl_rl_cfg_entry_point",
-                   help="Registry key of the runner cfg (rsl_rl_l2c2_cfg_entry_point: PPOL2C2 recipe).")
+                   help="Registry key of the runner cfg (rsl_rl_l2c2_cfg_entry_point: PPOL2C2 recipe; "
+                        "rsl_rl_lcp_cfg_entry_point: PPOLCP on the state task).")
     # AppLauncher flags the reference's train.sh passes; accepted for drop-in compatibility
     p.add_argument("--headless", action="store_true", default=False)
     p.add_argument("--enable_cameras", action="store_true", default=False)
