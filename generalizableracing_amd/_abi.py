@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 7
+GR_ABI_VERSION = 8
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -355,6 +355,14 @@ SIGNATURES = {
     # (mu, ld, act, ld, std, h1, z2, w1, w2, w3, rows, H, d, k, slope, ...)
     "gr_lcp_forward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 6),
     "gr_lcp_backward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 10),
+    "gr_offline_scratch_ints": (i64, [i64]),
+    # (feat, ld, aux, ld, n, d, features, supervision, capacity, cursor, scratch, stream)
+    "gr_offline_collect": (C.c_int, [vp, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp]),
+    "gr_offline_pgd_partials": (i64, [i64, i32]),
+    # (features, supervision, index, rows, d, wb, exp_avg, exp_avg_sq, step, epsilon, alpha, iters, lr, beta1, beta2,
+    #  eps, partial, loss_acc, x_adv, stream)
+    "gr_offline_pgd_step": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, vp, vp, f32, f32, i32, f64, f64, f64, f32, vp, vp,
+                                      vp, vp]),
     "gr_bn_scratch_doubles": (i64, [i64, i32]),
     "gr_bn_act_forward": (C.c_int, [vp, i64, i32, vp, vp, f32, i32, f32, vp, vp, vp, vp]),
     "gr_bn_act_backward": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp]),

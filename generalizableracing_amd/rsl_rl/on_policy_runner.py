@@ -274,6 +274,19 @@ class OnPolicyRunner:
             return lambda x: self.alg.policy.act_inference(self.obs_normalizer(x))  # noqa: E731
         return policy
 
+    def get_decoder(self, device=None):
+        """The auxiliary head on the fused feature (on_policy_runner.py:335-345): what the offline stage fine-tunes
+        (generalizableracing_amd.offline) and the exporters ship under a sigmoid."""
+        self.eval_mode()
+        if device is not None:
+            self.alg.policy.to(device)
+        decoder = self.alg.policy.aux_decoder
+        if self.cfg["empirical_normalization"]:
+            if device is not None:
+                self.obs_normalizer.to(device)
+            return lambda x: self.alg.policy.aux_decoder(self.obs_normalizer(x))  # noqa: E731
+        return decoder
+
     def train_mode(self):
         self.alg.policy.train()
         if self.empirical_normalization:

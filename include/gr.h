@@ -38,8 +38,9 @@ extern "C" {
 /* 2: GR_NUM_PLANES 17 (obstacle hint, rotor constants), gr_policy_args.precision, the observation sink and the
  * status word; gr_policy_args_size.  3: gr_stem1_* y_rows / gy_rows.  4: the gr_stem1_* / gr_stem12_* row indices
  * (`rows` after `off`).  5: gr_stem12_backward_w2 (conv2's weight gradient inside the first block's backward).
- * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward */
-#define GR_ABI_VERSION 7
+ * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward
+ * 8: gr_offline_collect / gr_offline_pgd_step */
+#define GR_ABI_VERSION 8
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -658,6 +659,47 @@ int gr_lcp_backward(const float* mu, int64_t ld_mu, const float* act, int64_t ld
                     int32_t hidden, int32_t d, int32_t k, float slope, const float* g, const float* v1,
                     const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
                     float* grads, void* stream);
+
+/* The offline auxiliary-head stage (standalone/offline/data_collector.py, standalone/offline/train.py): a balanced
+ * (feature, label) dataset kept on the device and the PGD-hardened fine-tune step of a Linear(d, 1) head on it.
+ * Context-free, on `stream`, graph-capturable, no allocation, no host synchronisation, no atomics.
+ *
+ * gr_offline_collect: one env step of data_collector.py:124-146.  feat [n][d] (row stride ld_feat floats), aux [n]
+ *   (row stride ld_aux floats; a label is positive when it is non-zero); the dataset features [capacity][d] fp32,
+ *   supervision [capacity] int8 (1 for a positive row, 0 for a zero-label row); cursor [3] int64 = rows, positives,
+ *   negatives written so far.  With w = cursor[0] on entry: P = the positive rows in ascending order, cut to
+ *   capacity - w when |P| > 0 and w + |P| >= capacity; written at w, w += |P|; Q = the zero-label rows in ascending
+ *   order, cut to |P| (after P's cut), then to capacity - w when w + |Q| >= capacity; written after P.  No positive:
+ *   nothing is written; a full dataset stays as it is.  One 1024-thread workgroup counts, then ranks every row by
+ *   ballot and popcount in row order and advances the cursor; a grid then copies one selected row per wave.  Dataset
+ *   offsets are 64-bit.  scratch: gr_offline_scratch_ints(n) int32, caller-owned.  n = 0 is a no-op.
+ *   GR_ERR_ARG: a null pointer, n < 0 or n > 2^30, d < 1, ld_feat < d, ld_aux < 1, capacity < 1.
+ *
+ * gr_offline_pgd_step: one mini-batch step of train.py's finetune_policy_head for a Linear(d, 1) head under
+ *   BCEWithLogitsLoss(mean).  Row i of the batch is dataset row index[i] (index null: row i); wb [d + 1] = the weight
+ *   then the bias; exp_avg / exp_avg_sq [d + 1] and step [1] (fp32 count) are Adam's state.  Per row, x0 the stored
+ *   feature, x = x0, `iters` times (pgd_attack, train.py:11-31, with dloss/dx = (sigmoid(z) - y) / rows * w):
+ *     z = w.x + b;  g = sigmoid(z) - y;  x_j += alpha sign(g) sign(w_j)  (sign(0) = 0);
+ *     x = clamp(x0 + clamp(x - x0, -epsilon, epsilon), 0, 1)          (iters = 0: x = clamp(x0, 0, 1))
+ *   then on the final x: loss = mean(softplus(z) - y z), gw = (1 / rows) sum_i g_i x_i, gb = (1 / rows) sum_i g_i,
+ *   and torch.optim.Adam's default update of wb (bias-corrected, eps outside the root, no weight decay), in place.
+ *   fp32 without contraction.  Two launches: a grid over the rows (one wave per row, the wave's rows in order, the
+ *   workgroup's waves in order) writes one partial row [gw (d) | gb | loss sum] per workgroup; one workgroup then
+ *   sums the partial rows in a fixed order and applies Adam: two runs give the same bits.  loss_acc [1] (double) +=
+ *   loss * rows (the epoch mean's numerator); x_adv [rows][d] (may be null) receives the final x.
+ *   partial: gr_offline_pgd_partials(rows, d) floats, caller-owned.
+ *   GR_ERR_ARG: a null pointer (but index / x_adv), rows < 1 or > 2^30, d < 1 or d > GR_OFFLINE_PGD_MAX_D,
+ *   iters < 0. */
+#define GR_OFFLINE_PGD_MAX_D 1024
+int64_t gr_offline_scratch_ints(int64_t n);
+int gr_offline_collect(const float* feat, int64_t ld_feat, const float* aux, int64_t ld_aux, int64_t n, int32_t d,
+                       float* features, int8_t* supervision, int64_t capacity, int64_t* cursor, int32_t* scratch,
+                       void* stream);
+int64_t gr_offline_pgd_partials(int64_t rows, int32_t d);
+int gr_offline_pgd_step(const float* features, const int8_t* supervision, const int64_t* index, int64_t rows,
+                        int32_t d, float* wb, float* exp_avg, float* exp_avg_sq, float* step, float epsilon,
+                        float alpha, int32_t iters, double lr, double beta1, double beta2, float eps, float* partial,
+                        double* loss_acc, float* x_adv, void* stream);
 
 /* The PPO losses of one mini-batch, forward and backward (standalone/rsl_rl/ext/algorithms/ppo.py:133-169: the
  * adaptive-rate KL, the clipped surrogate, the (clipped) value loss; the Gaussian log prob of rsl_rl's
