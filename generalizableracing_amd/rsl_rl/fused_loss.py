@@ -164,24 +164,32 @@ def policy_outputs(alg, obs, critic_obs):
     return pol.actor(obs), pol.critic(critic_obs)
 
 
-def ppo_loss(alg, obs, critic_obs, act, value_old, adv, ret, logp_old, mu_old, sig_old, acc=None, kl_out=None,
-             seed=None):
-    """(loss, [surrogate, value, KL] means) of one mini-batch: loss = surrogate + value_loss_coef * value
-    (- entropy_coef * entropy) as in ppo.py:171-172, differentiable; the same values as ppo_losses.  seed: the
-    device tensor autograd will be seeded with (the loss's gradient), when known now and the loss is the root: the
-    losses' backward then runs inside the forward's pass (gr_ppo_loss_forward_backward)."""
-    pol = alg.policy
-    mu, value = policy_outputs(alg, obs, critic_obs)
-    std = _policy_std(pol)
+def gaussian_entropy(std):
+    """Normal.entropy summed over the actions: with a state-independent std [k] the same for every sample."""
+    return (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
+
+
+def combined_loss(alg, mu, value, act, value_old, adv, ret, logp_old, mu_old, sig_old, acc=None, kl_out=None,
+                  seed=None, std=None):
+    """(loss, [surrogate, value, KL] means) of one mini-batch from the new policy's (action mean, value):
+    loss = surrogate + value_loss_coef * value (- entropy_coef * entropy) as in ppo.py:171-172, differentiable; the
+    same values as ppo_losses.  acc / kl_out: _PPOLossCombinedFn's device sinks.  seed: the device tensor autograd
+    will be seeded with (the loss's gradient), when known now and the loss is the root: the losses' backward then
+    runs inside the forward's pass (gr_ppo_loss_forward_backward).  std: _policy_std when the caller holds it."""
+    std = _policy_std(alg.policy) if std is None else std
     if alg.entropy_coef != 0.0:  # (the loss is not the root then: its gradient is not the seed)
         seed = None
     loss, stats = _PPOLossCombinedFn.apply(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old,
                                            float(alg.clip_param), bool(alg.use_clipped_value_loss),
                                            float(alg.value_loss_coef), acc, kl_out, seed)
-    if alg.entropy_coef != 0.0:  # Normal.entropy summed over the actions: the same for every sample
-        ent = (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
-        loss = loss - alg.entropy_coef * ent
+    if alg.entropy_coef != 0.0:
+        loss = loss - alg.entropy_coef * gaussian_entropy(std)
     return loss, stats
+
+
+def ppo_loss(alg, obs, critic_obs, *batch, **sinks):
+    """combined_loss of the policy's own forward (policy_outputs) on the mini-batch."""
+    return combined_loss(alg, *policy_outputs(alg, obs, critic_obs), *batch, **sinks)
 
 
 def fused_losses_ok(policy, obs: torch.Tensor) -> bool:
@@ -202,7 +210,4 @@ def ppo_losses(alg, obs, critic_obs, act, value_old, adv, ret, logp_old, mu_old,
     std = pol._std(mu[:1])[0]  # [k]: the scalar or exp(log) std, differentiable
     surr, vloss, kl = _PPOLossFn.apply(mu, std, value, act, logp_old, adv, value_old, ret, mu_old, sig_old,
                                        float(alg.clip_param), bool(alg.use_clipped_value_loss))
-    ent = None
-    if alg.entropy_coef != 0.0:  # Normal.entropy summed over the actions: the same for every sample
-        ent = (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
-    return surr, vloss, ent, kl, mu, std
+    return surr, vloss, gaussian_entropy(std) if alg.entropy_coef != 0.0 else None, kl, mu, std

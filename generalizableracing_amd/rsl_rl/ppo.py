@@ -9,6 +9,8 @@ applies the identical update.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.optim as optim
@@ -24,6 +26,14 @@ from .rollout_storage import RolloutStorage
 
 
 class PPO:
+    """One update for the family: `update` below drives every mini-batch step (eager loop or graphed replays);
+    a subclass supplies its storage and graphed-step classes, the names of its loss terms and `_minibatch_loss`."""
+
+    storage_cls = RolloutStorage
+    graphed_step_cls = None  # _GraphedStep (set below it)
+    # the mini-batch means update() averages, in the order _minibatch_loss returns them (an extra term goes last)
+    loss_terms = ("surrogate", "value_function")
+
     def __init__(self, policy, env=None, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998,
                  lam=0.95, value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
@@ -43,7 +53,7 @@ class PPO:
         # Adam (ppo.py:39) and the grad-norm clip as four device launches over the parameter table on CUDA
         # (flat_adam.py); torch.optim.Adam + nn.utils.clip_grad_norm_ on CPU or with fused_adam=False
         self.optimizer = _fadam.make_adam(self.policy.parameters(), learning_rate, fused=fused_adam)
-        self.transition = RolloutStorage.Transition()
+        self.transition = self.storage_cls.Transition()
         self.clip_param = clip_param
         self.num_learning_epochs = num_learning_epochs
         self.num_mini_batches = num_mini_batches
@@ -94,8 +104,8 @@ class PPO:
 
     def init_storage(self, training_type, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape,
                      action_shape):
-        self.storage = RolloutStorage(training_type, num_envs, num_transitions_per_env, actor_obs_shape,
-                                      critic_obs_shape, action_shape, self.device, obs_dtype=self.storage_obs_dtype)
+        self.storage = self.storage_cls(training_type, num_envs, num_transitions_per_env, actor_obs_shape,
+                                        critic_obs_shape, action_shape, self.device, obs_dtype=self.storage_obs_dtype)
         self._init_fused(num_envs)
 
     def _init_fused(self, num_envs):
@@ -141,36 +151,51 @@ class PPO:
             self.transition.clear()
             self.policy.reset(dones)
             return
-        self.transition.rewards = rewards.clone()
-        self.transition.dones = dones
-        if "time_outs" in infos:  # bootstrapping on time outs (ppo.py:88-92)
-            self.transition.rewards += self.gamma * torch.squeeze(
-                self.transition.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
+        self._stage_rewards(rewards, dones, infos)
         self.storage.add_transitions(self.transition)
         self.transition.clear()
         self.policy.reset(dones)
+
+    def _stage_rewards(self, rewards, dones, infos):
+        """The step's rewards and dones into the transition, bootstrapping on time outs (ppo.py:88-92)."""
+        self.transition.rewards = rewards.clone()
+        self.transition.dones = dones
+        if "time_outs" in infos:
+            self.transition.rewards += self.gamma * torch.squeeze(
+                self.transition.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
 
     def compute_returns(self, last_critic_obs):
         last_values = self.policy.evaluate(last_critic_obs).detach()
         self.storage.compute_returns(last_values, self.gamma, self.lam, self.normalize_advantage)
 
-    def _adapt_learning_rate(self, mu_batch, sigma_batch, old_mu_batch, old_sigma_batch):
-        """Adaptive KL learning rate (ppo.py:133-150); KL mean averaged over ranks."""
-        if self.desired_kl is None or self.schedule != "adaptive":
+    def _adaptive(self) -> bool:
+        return self.desired_kl is not None and self.schedule == "adaptive"
+
+    def _kl_mean(self, mu, sigma, mu_old, sig_old, out=None):
+        """The mini-batch's mean KL between the old and the new Gaussians (ppo.py:133-141), None off the adaptive
+        schedule; written to out [1] when given (the graphed step's device sink)."""
+        if not self._adaptive():
+            return None
+        with torch.no_grad():
+            kl = torch.sum(torch.log(sigma / sig_old + 1.0e-5)
+                           + (torch.square(sig_old) + torch.square(mu_old - mu)) / (2.0 * torch.square(sigma)) - 0.5,
+                           axis=-1)
+            kl = torch.mean(kl)
+            if out is not None:
+                out[0].copy_(kl)
+        return kl
+
+    def _adapt_learning_rate(self, kl_mean):
+        """Adaptive KL learning rate (ppo.py:142-150) on the host; the KL mean is averaged over ranks first."""
+        if not self._adaptive():
             return
-        with torch.inference_mode():
-            kl = torch.sum(
-                torch.log(sigma_batch / old_sigma_batch + 1.0e-5)
-                + (torch.square(old_sigma_batch) + torch.square(old_mu_batch - mu_batch))
-                / (2.0 * torch.square(sigma_batch)) - 0.5, axis=-1)
-            kl_mean = gdist.allreduce_mean(torch.mean(kl))
-            kl_val = float(kl_mean)  # host decision, as in the reference
-            if kl_val > self.desired_kl * 2.0:
-                self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-            elif self.desired_kl / 2.0 > kl_val > 0.0:
-                self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-            for g in self.optimizer.param_groups:
-                g["lr"] = self.learning_rate
+        kl_val = float(gdist.allreduce_mean(kl_mean.detach()))  # host decision, as in the reference
+        if kl_val > self.desired_kl * 2.0:
+            self.learning_rate = max(1e-5, self.learning_rate / 1.5)
+        elif self.desired_kl / 2.0 > kl_val > 0.0:
+            self.learning_rate = min(1e-2, self.learning_rate * 1.5)
+        for g in self.optimizer.param_groups:
+            g["lr"] = self.learning_rate
 
     def _ppo_losses(self, actions_log_prob_batch, old_actions_log_prob_batch, advantages_batch, value_batch,
                     target_values_batch, returns_batch):
@@ -207,34 +232,20 @@ class PPO:
         return self.flat_grads()
 
     def update(self):
-        if self.graph_update and self.storage is not None and str(self.device).startswith("cuda") \
-                and type(self).update is PPO.update:
+        if self.graph_update and self.storage is not None and str(self.device).startswith("cuda"):
             if self._graphed is None:
-                self._graphed = _GraphedStep(self)
+                self._graphed = self.graphed_step_cls(self)
             out = self._graphed.update()
             if self.fused is not None:  # graph replays write the parameters without bumping their versions
                 self.fused.refresh()
             return out
-        mean_value_loss = torch.zeros((), device=self.device)
-        mean_surrogate_loss = torch.zeros((), device=self.device)
+        sums = [torch.zeros((), device=self.device) for _ in self.loss_terms]
         generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         params = list(self.policy.parameters())
         flat = self.flat_grads()
         flat.bind()
-        ac = torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.update_autocast_bf16 and
-                            str(self.device).startswith("cuda"))
-        for (obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
-             old_actions_log_prob_batch, old_mu_batch, old_sigma_batch, hid_states_batch, masks_batch) in generator:
-            if self._use_fused_losses(obs_batch):  # the same losses as one device op each way (fused_loss.py)
-                loss, stats = _floss.ppo_loss(
-                    self, obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch,
-                    returns_batch, old_actions_log_prob_batch, old_mu_batch, old_sigma_batch)
-                surrogate_loss, value_loss = stats[0], stats[1]
-                self._adapt_learning_rate_kl(stats[2])
-            else:
-                surrogate_loss, value_loss, loss = self._torch_losses(
-                    ac, obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch,
-                    returns_batch, old_actions_log_prob_batch, old_mu_batch, old_sigma_batch)
+        for batch in generator:
+            loss, terms, kl = self._minibatch_loss(batch)
             self.optimizer.zero_grad(set_to_none=False)  # (in place: the views of the flat buffer stay bound)
             if not self._grads_checked:
                 flat = self._check_all_grads(loss, params)
@@ -244,50 +255,55 @@ class PPO:
                 raise RuntimeError("PPO.update: a parameter the loss did not reach on the first mini-batch now has a "
                                    "gradient; the set of parameters the loss reaches must be fixed from the first "
                                    "mini-batch (it is checked once: _check_all_grads)")
+            self._adapt_learning_rate(kl)  # (the rate only enters optimizer.step; ahead of the gradients' exchange)
             gdist.allreduce_grads(params, flat)
             _fadam.clip_grad_norm_(self.optimizer, params, self.max_grad_norm)
             self.optimizer.step()
-            mean_value_loss += value_loss.detach()
-            mean_surrogate_loss += surrogate_loss.detach()
-        num_updates = self.num_learning_epochs * self.num_mini_batches
+            for s, t in zip(sums, terms):
+                s += t
         self.storage.clear()
-        return {
-            "value_function": float(mean_value_loss) / num_updates,
-            "surrogate": float(mean_surrogate_loss) / num_updates,
-        }
+        return self._stats([float(s) for s in sums])
+
+    def _stats(self, sums):
+        """update()'s result from the sums of the mini-batch means (in loss_terms order)."""
+        n = self.num_learning_epochs * self.num_mini_batches
+        mean = {k: v / n for k, v in zip(self.loss_terms, sums)}
+        return {k: mean[k] for k in ("value_function", "surrogate") + self.loss_terms[2:]}
 
     def _use_fused_losses(self, obs) -> bool:
         return (self.fused_losses and obs.is_cuda and not self.update_autocast_bf16
                 and _floss.fused_losses_ok(self.policy, obs))
 
-    def _adapt_learning_rate_kl(self, kl_mean):
-        """_adapt_learning_rate from the mini-batch's KL mean (computed by the fused losses)."""
-        if self.desired_kl is None or self.schedule != "adaptive":
-            return
-        kl_val = float(gdist.allreduce_mean(kl_mean.detach()))  # host decision, as in the reference
-        if kl_val > self.desired_kl * 2.0:
-            self.learning_rate = max(1e-5, self.learning_rate / 1.5)
-        elif self.desired_kl / 2.0 > kl_val > 0.0:
-            self.learning_rate = min(1e-2, self.learning_rate * 1.5)
-        for g in self.optimizer.param_groups:
-            g["lr"] = self.learning_rate
+    def _minibatch_loss(self, batch, acc=None, kl_out=None, seed=None):
+        """(loss, terms, KL mean) of one mini-batch, `batch` as the storage's generator yields it (the graphed step
+        gathers the same fields).  terms: the detached means named by loss_terms.  The eager loop passes nothing
+        else.  The graphed step passes its device sinks, and nothing here may then read back to the host: acc holds
+        the update's sums of the terms (a path whose fused op adds to it adds all its terms and returns none), the KL
+        mean goes to kl_out [1] too (given on the adaptive schedule only; the return value is not read), and seed is
+        the tensor autograd will be seeded with, for a loss that is its root (fused_loss.combined_loss)."""
+        if self._use_fused_losses(batch[0]):  # the same losses as one device op each way (fused_loss.py)
+            loss, stats = _floss.ppo_loss(self, *batch[:9], acc=acc, kl_out=kl_out, seed=seed)
+            return loss, () if acc is not None else (stats[0], stats[1]), stats[2]
+        autocast = self.update_autocast_bf16 and str(self.device).startswith("cuda")
+        return self._torch_ppo_loss(*batch[:9], kl_out, draw=acc is None, autocast=autocast)[:3]
 
-    def _torch_losses(self, ac, obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch,
-                      returns_batch, old_actions_log_prob_batch, old_mu_batch, old_sigma_batch):
-        """ppo.py:103-169 as torch ops (CPU, autocast, other policies)."""
-        with ac:
-                self.policy.act(obs_batch)
-                actions_log_prob_batch = self.policy.get_actions_log_prob(actions_batch)
-                value_batch = self.policy.evaluate(critic_obs_batch)
-                mu_batch = self.policy.action_mean
-                sigma_batch = self.policy.action_std
-                entropy_batch = self.policy.entropy
-        self._adapt_learning_rate(mu_batch.float(), sigma_batch.float(), old_mu_batch, old_sigma_batch)
-        surrogate_loss, value_loss = self._ppo_losses(actions_log_prob_batch.float(), old_actions_log_prob_batch,
-                                                      advantages_batch, value_batch.float(), target_values_batch,
-                                                      returns_batch)
-        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_batch.float().mean()
-        return surrogate_loss, value_loss, loss
+    def _torch_ppo_loss(self, obs, critic_obs, act, val, adv, ret, logp_old, mu_old, sig_old, kl_out=None, draw=True,
+                        autocast=False):
+        """ppo.py:103-172 as torch ops (CPU, autocast, other policies): _minibatch_loss's triple, then the action
+        mean and the value.  draw: through policy.act, whose sample nobody uses but which advances the generator as
+        the reference does (the eager loops); torch.normal's check of the std reads back to the host, which a capture
+        forbids, so the graphed steps only set the distribution."""
+        pol = self.policy
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            pol.act(obs) if draw else pol.update_distribution(obs)
+            logp = pol.get_actions_log_prob(act)
+            value = pol.evaluate(critic_obs)
+            mu, sigma, entropy = pol.action_mean, pol.action_std, pol.entropy
+        logp, value, mu, sigma, entropy = (t.float() for t in (logp, value, mu, sigma, entropy))
+        kl = self._kl_mean(mu, sigma, mu_old, sig_old, kl_out)
+        surrogate_loss, value_loss = self._ppo_losses(logp, logp_old, adv, value, val, ret)
+        loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+        return loss, (surrogate_loss.detach(), value_loss.detach()), kl, mu, value
 
 
 class _GraphedStep:
@@ -348,7 +364,7 @@ class _GraphedStep:
         self.cols = st.sample_columns() if self._PACK else None
         # persistent: the graphs read it (the storage's own packed buffer, shared with the eager generator)
         self.pack = st.pack_samples(out=st.packed_buffer()) if self.cols is not None else None
-        self.acc = torch.zeros(2, device=dev)  # the update's sums of the surrogate and value means
+        self.acc = torch.zeros(len(alg.loss_terms), device=dev)  # the update's sums of the loss terms' means
         self.one = torch.ones((), device=dev)
         self.segmented = gdist.is_dist() or alg.graph_update_segmented
         self.per_step = self.segmented or alg.graph_update_per_step
@@ -370,43 +386,28 @@ class _GraphedStep:
         if self.cols is not None:
             g = self.pack.index_select(0, idx)
             return tuple(g[:, a:b] for a, b in self.cols)
-        return tuple(x.index_select(0, idx) for x in st.sample_sources())
+        g = tuple(x.index_select(0, idx) for x in st.sample_sources())
+        return (g[0].float(), g[1].float()) + g[2:]  # (fp32 observations, as the generator yields them)
 
-    def _adaptive(self) -> bool:
-        return self.alg.desired_kl is not None and self.alg.schedule == "adaptive"
+    @contextlib.contextmanager
+    def _grad_sink(self):
+        """While set, the fused ops write their gradients into the flat buffer's views directly
+        (linear._GRAD_SINK): the step copies only the others."""
+        _lin._GRAD_SINK = {id(p): v for p, v in zip(self.flat.params, self.flat.views)}
+        try:
+            yield
+        finally:
+            _lin._GRAD_SINK = None
 
     def _seg_a(self, idx=None):
-        alg, pol = self.alg, self.alg.policy
-        obs, priv, act, val, adv, ret, logp, mu, sig = self._gather(self.idx if idx is None else idx)
-        obs, priv = obs.float(), priv.float()
-        if alg._use_fused_losses(obs):  # (fused_loss.py: one device op each way, the means and the loss finished
-            # there: the step's loss sums accumulate in self.acc, the KL mean lands in the flat buffer's extra slot)
-            # (the gradients land in the flat buffer's views directly while the sink is set: linear._GRAD_SINK)
-            _lin._GRAD_SINK = {id(p): v for p, v in zip(self.flat.params, self.flat.views)}
-            try:
-                loss, _ = _floss.ppo_loss(alg, obs, priv, act, val, adv, ret, logp, mu, sig, acc=self.acc,
-                                          kl_out=self.flat.extra[:1] if self._adaptive() else None, seed=self.one)
-            finally:
-                _lin._GRAD_SINK = None
-            self._backward(loss)
-            return
-        # the eager loop's policy.act also draws a sample it never uses; torch.normal's check of the std
-        # reads back to the host, which a capture forbids, so only the distribution is set here
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=alg.update_autocast_bf16):
-            pol.update_distribution(obs)
-            logp_b = pol.get_actions_log_prob(act)
-            value_b = pol.evaluate(priv)
-            mu_b, sigma_b, entropy_b = pol.action_mean, pol.action_std, pol.entropy
-        logp_b, value_b, mu_b, sigma_b, entropy_b = (t.float() for t in (logp_b, value_b, mu_b, sigma_b, entropy_b))
-        if self._adaptive():
-            with torch.no_grad():
-                kl = torch.sum(torch.log(sigma_b / sig + 1.0e-5)
-                               + (torch.square(sig) + torch.square(mu - mu_b)) / (2.0 * torch.square(sigma_b)) - 0.5,
-                               axis=-1)
-                self.flat.extra[0].copy_(torch.mean(kl))
-        surrogate_loss, value_loss = alg._ppo_losses(logp_b, logp, adv, value_b, val, ret)
-        loss = surrogate_loss + alg.value_loss_coef * value_loss - alg.entropy_coef * entropy_b.mean()
-        self.acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach()]))
+        """Gather, the algorithm's loss with the device sinks (PPO._minibatch_loss), backward."""
+        alg = self.alg
+        batch = self._gather(self.idx if idx is None else idx)
+        with self._grad_sink():  # (a seeded fused loss has its gradients in its forward already)
+            loss, terms, _ = alg._minibatch_loss(batch, acc=self.acc, seed=self.one,
+                                                 kl_out=self.flat.extra[:1] if alg._adaptive() else None)
+        if terms:  # (the torch ops: no fused op has added them up)
+            self.acc.add_(torch.stack(terms))
         self._backward(loss)
 
     def _backward(self, loss):
@@ -415,13 +416,8 @@ class _GraphedStep:
             grads = torch.autograd.grad(loss, self.params, retain_graph=True, allow_unused=True)
             self.flat = alg._check_all_grads(loss, self.params, grads)
             self.flat.bind()
-        # (the seed gradient from a persistent 1: no fill launch in the captured step; the fused MLP backward writes
-        # its gradients into their flat views directly, linear._GRAD_SINK, and only the others are copied)
-        _lin._GRAD_SINK = {id(p): v for p, v in zip(self.flat.params, self.flat.views)}
-        try:
+        with self._grad_sink():  # (the seed gradient from a persistent 1: no fill launch in the captured step)
             grads = torch.autograd.grad(loss, self.flat.params, grad_outputs=self.one)
-        finally:
-            _lin._GRAD_SINK = None
         pairs = [(v, g) for v, g in zip(self.flat.views, grads) if g.data_ptr() != v.data_ptr()]
         if pairs:
             torch._foreach_copy_([v for v, _ in pairs], [g for _, g in pairs])
@@ -429,10 +425,10 @@ class _GraphedStep:
     def _seg_b(self):
         alg = self.alg
         if isinstance(self.opt, _fadam.FlatAdam):  # the rate rule, the clip and Adam: two launches (gr_adam_clip_step)
-            self.opt.clip_and_step(alg.max_grad_norm, kl=self.flat.extra if self._adaptive() else None,
+            self.opt.clip_and_step(alg.max_grad_norm, kl=self.flat.extra if alg._adaptive() else None,
                                    desired_kl=alg.desired_kl)
             return
-        if self._adaptive():  # on the rank-averaged KL mean once the flat buffer has been all-reduced: the
+        if alg._adaptive():  # on the rank-averaged KL mean once the flat buffer has been all-reduced: the
             # comparisons of ppo.py:133-150 on the device, one launch (gr_adaptive_lr)
             _abi.call("gr_adaptive_lr", self.flat.extra.data_ptr(), self.lr.data_ptr(), alg.desired_kl, 1e-5, 1e-2,
                       _abi.raw_stream(self.lr.device))
@@ -501,10 +497,6 @@ class _GraphedStep:
         if self.pack is not None:
             self.alg.storage.pack_samples(out=self.pack)
 
-    def _stats(self, num_updates):
-        sl, vl = self.acc.tolist()
-        return {"value_function": vl / num_updates, "surrogate": sl / num_updates}
-
     def update(self):
         alg = self.alg
         n = alg.num_mini_batches
@@ -540,7 +532,9 @@ class _GraphedStep:
                 if self.graph_b is not None:
                     self.flat.allreduce_()  # eager, on the current stream's order: gradients + KL mean, one message
                     self.graph_b.replay()
-        num_updates = alg.num_learning_epochs * n
         alg.learning_rate = float(self.lr)
         alg.storage.clear()
-        return self._stats(num_updates)
+        return alg._stats(self.acc.tolist())
+
+
+PPO.graphed_step_cls = _GraphedStep

@@ -23,14 +23,10 @@ Deviations (documented):
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 
 from .. import _abi
-from . import distributed as gdist
-from . import flat_adam as _fadam
 from . import fused_loss as _floss
 from .ppo import PPO, _GraphedStep
 from .rollout_storage_l2c2 import RolloutStorageL2C2
@@ -68,6 +64,9 @@ def _mix_rows(src, rows_obs, rows_next, w):
 
 
 class PPOL2C2(PPO):
+    storage_cls = RolloutStorageL2C2
+    loss_terms = PPO.loss_terms + ("smooth_loss",)
+
     def __init__(self, policy, env=None, value_smoothness_coef=0.1, smoothness_upper_bound=1.0,
                  smoothness_lower_bound=0.1, share_mix_features=True, rows_update=True, **kwargs):
         kwargs.pop("normalize_advantage", None)
@@ -76,18 +75,10 @@ class PPOL2C2(PPO):
         # the graphed update reads the mini-batch's image rows through its permutation (no gathered copies)
         self.rows_update = bool(rows_update)
         super().__init__(policy, env=env, normalize_advantage=True, **kwargs)
-        self.transition = RolloutStorageL2C2.Transition()
         self._mix_uniform = torch.rand_like  # the smoothness loss's uniform draw (tests substitute a fixed one)
         self.value_smoothness_coef = value_smoothness_coef
         self.smoothness_upper_bound = smoothness_upper_bound
         self.smoothness_lower_bound = smoothness_lower_bound
-
-    def init_storage(self, training_type, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape,
-                     action_shape):
-        self.storage = RolloutStorageL2C2(training_type, num_envs, num_transitions_per_env, actor_obs_shape,
-                                          critic_obs_shape, action_shape, self.device,
-                                          obs_dtype=self.storage_obs_dtype)
-        self._init_fused(num_envs)
 
     def smooth_coefs(self):
         """ppo_l2c2.py:176-178."""
@@ -127,11 +118,7 @@ class PPOL2C2(PPO):
         return super().act(obs, critic_obs)
 
     def process_env_step(self, rewards, dones, infos):
-        self.transition.rewards = rewards.clone()
-        self.transition.dones = dones
-        if "time_outs" in infos:  # ppo_l2c2.py:91-95
-            self.transition.rewards += self.gamma * torch.squeeze(
-                self.transition.values * infos["time_outs"].unsqueeze(1).to(self.device), 1)
+        self._stage_rewards(rewards, dones, infos)  # ppo_l2c2.py:91-95
         sink = getattr(self.storage, "sink", False)
         store = self._stored()  # ppo_l2c2.py:98
         del self._store_flag
@@ -180,56 +167,33 @@ class PPOL2C2(PPO):
             action_smoothness = torch.norm(mu_batch - next_mean, dim=-1).mean()
         return loss, action_smoothness
 
-    def update(self):
-        if self.graph_update and self.storage is not None and str(self.device).startswith("cuda"):
-            if self._graphed is None:
-                self._graphed = _GraphedStepL2C2(self)
-            out = self._graphed.update()
-            if self.fused is not None:  # graph replays write the parameters without bumping their versions
-                self.fused.refresh()
-            return out
-        mean_value_loss = torch.zeros((), device=self.device)
-        mean_surrogate_loss = torch.zeros((), device=self.device)
-        mean_smooth_loss = torch.zeros((), device=self.device)
-        generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-        params = list(self.policy.parameters())
-        flat = self.flat_grads()
-        flat.bind()
-        for (obs_batch, critic_obs_batch, next_obs_batch, cont_batch, actions_batch, target_values_batch,
-             advantages_batch, returns_batch, old_actions_log_prob_batch, old_mu_batch, old_sigma_batch,
-             hid_states_batch, masks_batch) in generator:
-            self.policy.act(obs_batch)
-            actions_log_prob_batch = self.policy.get_actions_log_prob(actions_batch)
-            value_batch = self.policy.evaluate(critic_obs_batch)
-            mu_batch = self.policy.action_mean
-            sigma_batch = self.policy.action_std
-            entropy_batch = self.policy.entropy
-            self._adapt_learning_rate(mu_batch, sigma_batch, old_mu_batch, old_sigma_batch)
-            surrogate_loss, value_loss = self._ppo_losses(actions_log_prob_batch, old_actions_log_prob_batch,
-                                                          advantages_batch, value_batch, target_values_batch,
-                                                          returns_batch)
-            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_batch.mean()
-            smooth_loss, _ = self.smooth_loss(obs_batch, next_obs_batch, cont_batch, mu_batch, value_batch,
-                                              want_smoothness=False)
-            loss = loss + smooth_loss
-            self.optimizer.zero_grad(set_to_none=False)
-            if not self._grads_checked:
-                flat = self._check_all_grads(loss, params)
-                flat.bind()
-            loss.backward()
-            gdist.allreduce_grads(params, flat)
-            _fadam.clip_grad_norm_(self.optimizer, params, self.max_grad_norm)
-            self.optimizer.step()
-            mean_value_loss += value_loss.detach()
-            mean_surrogate_loss += surrogate_loss.detach()
-            mean_smooth_loss += smooth_loss.detach()
-        num_updates = self.num_learning_epochs * self.num_mini_batches
-        self.storage.clear()
-        return {
-            "value_function": float(mean_value_loss) / num_updates,
-            "surrogate": float(mean_surrogate_loss) / num_updates,
-            "smooth_loss": float(mean_smooth_loss) / num_updates,
-        }
+    def _use_fused_losses(self, obs) -> bool:
+        """The graphed step's PPO losses as one device op each way (fused_loss.combined_loss): a policy with actor /
+        critic heads and a state-independent std over <= 8 actions, fp32 outside autocast."""
+        pol = self.policy
+        return (self.fused_losses and obs.is_cuda and obs.dtype == torch.float32 and hasattr(pol, "features")
+                and isinstance(pol.actor, nn.Sequential) and pol.actor[-1].out_features <= 8
+                and getattr(pol, "noise_std_type", None) in ("scalar", "log")
+                and not torch.is_autocast_enabled("cuda"))
+
+    def _minibatch_loss(self, batch, acc=None, kl_out=None, seed=None):
+        """PPO._minibatch_loss plus the smoothness loss (ppo_l2c2.py:127-191).  The eager loop takes the torch ops,
+        without autocast.  The graphed step may hand obs, critic obs and next obs each as a (storage rows, indices)
+        pair, read through the indices (_GraphedStepL2C2._gather).  seed is unused: the loss is never the root."""
+        obs, crit, nxt, cont = batch[:4]
+        pol = self.policy
+        rows = (obs[0], obs[1], nxt[1]) if isinstance(obs, tuple) else None
+        if rows is not None or (acc is not None and self._use_fused_losses(obs)):
+            # the log prob, KL, surrogate and value losses in one launch each way, into the sinks
+            feat = (lambda x: pol.features_rows(*x)) if rows is not None else pol.features
+            mu_b, value_b = pol.actor(feat(obs)), pol.critic(feat(crit))
+            loss, _ = _floss.combined_loss(self, mu_b, value_b, *batch[4:11], acc=acc[:2], kl_out=kl_out)
+            smooth_loss, _ = self.smooth_loss(obs, nxt, cont, mu_b, value_b, rows=rows, want_smoothness=False)
+            acc[2:].add_(smooth_loss.detach())
+            return loss + smooth_loss, (), None
+        loss, terms, kl, mu_b, value_b = self._torch_ppo_loss(obs, crit, *batch[4:11], kl_out, draw=acc is None)
+        smooth_loss, _ = self.smooth_loss(obs, nxt, cont, mu_b, value_b, want_smoothness=False)
+        return loss + smooth_loss, terms + (smooth_loss.detach(),), kl
 
 
 class _GraphedStepL2C2(_GraphedStep):
@@ -255,7 +219,6 @@ class _GraphedStepL2C2(_GraphedStep):
         self.mb = (self.T - 1) * self.N // self.nmb
         self.perm = torch.zeros(self.nmb * self.mb, dtype=torch.long, device=dev)
         self.idx = self.perm[:self.mb]
-        self.acc = torch.zeros(3, device=dev)  # the update's sums of the surrogate, value and smoothness means
         self.cont = torch.zeros((self.T - 1) * self.N, 1, device=dev)
 
     def _refresh_sources(self):
@@ -272,16 +235,17 @@ class _GraphedStepL2C2(_GraphedStep):
                                                st.mu, st.sigma))
 
     def _gather(self, idx):
-        return tuple(x.index_select(0, idx) for x in self._sources())
-
-    def _fused_losses_ok(self, obs) -> bool:
-        """The PPO losses as one device op each way (fused_loss._PPOLossCombinedFn, as PPO's graphed step uses them):
-        a policy with actor / critic heads and a state-independent std over <= 8 actions, fp32 outside autocast."""
-        pol = self.alg.policy
-        return (self.alg.fused_losses and obs.is_cuda and obs.dtype == torch.float32 and hasattr(pol, "features")
-                and isinstance(pol.actor, nn.Sequential) and pol.actor[-1].out_features <= 8
-                and getattr(pol, "noise_std_type", None) in ("scalar", "log")
-                and not torch.is_autocast_enabled("cuda"))
+        """The generator's fields by a static index buffer; the three image fields as (storage rows, indices) pairs
+        instead when the rows can be read through the permutation (_rows_ok: the same values, no gathered copies)."""
+        srcs = self._sources()
+        if not self._rows_ok():
+            g = tuple(x.index_select(0, idx) for x in srcs)
+            return tuple(x.float() for x in g[:3]) + g[3:]
+        st = self.alg.storage
+        src = st.observations.flatten(0, 1)  # row j + N is the successor of row j
+        csrc = st.privileged_observations.flatten(0, 1) if st.privileged_observations is not None else src
+        nidx = idx + self.N
+        return ((src, idx), (csrc, idx), (src, nidx)) + tuple(x.index_select(0, idx) for x in srcs[3:])
 
     def _rows_ok(self) -> bool:
         """The mini-batch's image rows read through the permutation (VisionActorCritic.features_rows, the fused
@@ -291,70 +255,7 @@ class _GraphedStepL2C2(_GraphedStep):
         srcs = [st.observations] + ([st.privileged_observations] if st.privileged_observations is not None else [])
         return (self.alg.rows_update and hasattr(pol, "features_rows") and st.observations.is_cuda
                 and all(x.dtype == torch.float32 and x.is_contiguous() for x in srcs)
-                and st.observations.shape[-1] % 4 == 0 and self._fused_losses_ok(st.observations[0]))
+                and st.observations.shape[-1] % 4 == 0 and self.alg._use_fused_losses(st.observations[0]))
 
-    def _seg_a_rows(self, idx):
-        """Segment A with the image rows read through `idx` (the same values as the gathered form)."""
-        alg, pol, st = self.alg, self.alg.policy, self.alg.storage
-        src = st.observations.flatten(0, 1)  # row j + N is the successor of row j
-        csrc = st.privileged_observations.flatten(0, 1) if st.privileged_observations is not None else src
-        nidx = idx + self.N
-        cont, act, val, adv, ret, logp, mu, sig = (x.index_select(0, idx) for x in self._sources()[3:])
-        mu_b = pol.actor(pol.features_rows(src, idx))
-        value_b = pol.critic(pol.features_rows(csrc, idx))
-        std = _floss._policy_std(pol)
-        loss, _ = _floss._PPOLossCombinedFn.apply(
-            mu_b, std, value_b, act, logp, adv, val, ret, mu, sig, float(alg.clip_param),
-            bool(alg.use_clipped_value_loss), float(alg.value_loss_coef), self.acc[:2],
-            self.flat.extra[:1] if self._adaptive() else None, None)
-        if alg.entropy_coef != 0.0:
-            loss = loss - alg.entropy_coef * (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
-        smooth_loss, _ = alg.smooth_loss(None, None, cont, mu_b, value_b, rows=(src, idx, nidx),
-                                         want_smoothness=False)
-        self.acc[2:].add_(smooth_loss.detach())
-        self._backward(loss + smooth_loss)
 
-    def _seg_a(self, idx=None):
-        alg, pol = self.alg, self.alg.policy
-        idx = self.idx if idx is None else idx
-        if self._rows_ok():
-            self._seg_a_rows(idx)
-            return
-        obs, crit, nxt, cont, act, val, adv, ret, logp, mu, sig = self._gather(idx)
-        obs, crit, nxt = obs.float(), crit.float(), nxt.float()
-        if self._fused_losses_ok(obs):
-            # ppo_l2c2.py:127-175 with the log prob, KL, surrogate and value losses in one launch each way; the KL
-            # mean lands in the flat buffer's extra slot, the surrogate and value means accumulate in acc[:2]
-            mu_b = pol.actor(pol.features(obs))
-            value_b = pol.critic(pol.features(crit))
-            std = _floss._policy_std(pol)
-            loss, _ = _floss._PPOLossCombinedFn.apply(
-                mu_b, std, value_b, act, logp, adv, val, ret, mu, sig, float(alg.clip_param),
-                bool(alg.use_clipped_value_loss), float(alg.value_loss_coef), self.acc[:2],
-                self.flat.extra[:1] if self._adaptive() else None, None)
-            if alg.entropy_coef != 0.0:  # Normal.entropy summed over the actions: the same for every sample
-                loss = loss - alg.entropy_coef * (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
-            smooth_loss, _ = alg.smooth_loss(obs, nxt, cont, mu_b, value_b, want_smoothness=False)
-            self.acc[2:].add_(smooth_loss.detach())
-            self._backward(loss + smooth_loss)
-            return
-        pol.update_distribution(obs)
-        logp_b = pol.get_actions_log_prob(act)
-        value_b = pol.evaluate(crit)
-        mu_b, sigma_b, entropy_b = pol.action_mean, pol.action_std, pol.entropy
-        if self._adaptive():
-            with torch.no_grad():
-                kl = torch.sum(torch.log(sigma_b / sig + 1.0e-5)
-                               + (torch.square(sig) + torch.square(mu - mu_b)) / (2.0 * torch.square(sigma_b)) - 0.5,
-                               axis=-1)
-                self.flat.extra[0].copy_(torch.mean(kl))
-        surrogate_loss, value_loss = alg._ppo_losses(logp_b, logp, adv, value_b, val, ret)
-        loss = surrogate_loss + alg.value_loss_coef * value_loss - alg.entropy_coef * entropy_b.mean()
-        smooth_loss, _ = alg.smooth_loss(obs, nxt, cont, mu_b, value_b, want_smoothness=False)
-        loss = loss + smooth_loss
-        self.acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach(), smooth_loss.detach()]))
-        self._backward(loss)
-
-    def _stats(self, num_updates):
-        sl, vl, ml = self.acc.tolist()
-        return {"value_function": vl / num_updates, "surrogate": sl / num_updates, "smooth_loss": ml / num_updates}
+PPOL2C2.graphed_step_cls = _GraphedStepL2C2

@@ -22,15 +22,11 @@ update_autocast_bf16.
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.distributions import Normal
 
-from . import distributed as gdist
-from . import flat_adam as _fadam
 from . import fused_lcp as _flcp
 from . import fused_loss as _floss
 from . import linear as _lin
@@ -55,6 +51,8 @@ def actor_plain(actor: nn.Module, x: torch.Tensor) -> torch.Tensor:
 
 
 class PPOLCP(PPO):
+    loss_terms = PPO.loss_terms + ("grad_penalty",)
+
     def __init__(self, policy, env=None, grad_penalty_coef_schedule=None, **kwargs):
         # (required, and asserted, as in ppo_lcp.py:59)
         assert grad_penalty_coef_schedule is not None, "PPOLCP: grad_penalty_coef_schedule is required"
@@ -89,11 +87,8 @@ class PPOLCP(PPO):
         pol = self.policy
         mu, value, h1, z2 = _lin.fused_mlps([pol.actor, pol.critic], [obs, critic_obs], extras=True)
         std = _floss._policy_std(pol)
-        loss, stats = _floss._PPOLossCombinedFn.apply(
-            mu, std, value, act, logp_old, adv, val, ret, mu_old, sig_old, float(self.clip_param),
-            bool(self.use_clipped_value_loss), float(self.value_loss_coef), acc, kl_out, None)
-        if self.entropy_coef != 0.0:  # Normal.entropy summed over the actions: the same for every sample
-            loss = loss - self.entropy_coef * (0.5 + 0.5 * math.log(2.0 * math.pi) + torch.log(std)).sum()
+        loss, stats = _floss.combined_loss(self, mu, value, act, val, adv, ret, logp_old, mu_old, sig_old, acc=acc,
+                                           kl_out=kl_out, std=std)
         pen = _flcp.lcp_penalty(pol.actor, mu, std, act.float(), h1, z2)
         self.fused_penalty_steps += 1
         return loss + coef * pen, stats, pen
@@ -114,94 +109,41 @@ class PPOLCP(PPO):
         loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_b.mean() + coef * pen
         return loss, surrogate_loss, value_loss, pen, mu_b, sigma_b
 
-    # ---------------------------------------------------------------------------------------------- update
+    def _minibatch_loss(self, batch, acc=None, kl_out=None, seed=None):
+        """PPO._minibatch_loss plus coef * P.  The graphed step's coefficient is its device scalar; seed is unused:
+        the loss is never the root."""
+        coef = self._graphed.coef if acc is not None else self.gradient_penalty_coef()
+        if self._use_fused_penalty(batch[0], batch[1]):
+            loss, stats, pen = self._fused_lcp_loss(*batch[:9], coef, acc=None if acc is None else acc[:2],
+                                                    kl_out=kl_out)
+            if acc is not None:
+                acc[2:].add_(pen.detach())
+                return loss, (), None
+            return loss, (stats[0], stats[1], pen.detach()), stats[2]
+        loss, surrogate_loss, value_loss, pen, mu, sigma = self._torch_lcp_loss(*batch[:7], coef)
+        return (loss, (surrogate_loss.detach(), value_loss.detach(), pen.detach()),
+                self._kl_mean(mu, sigma, *batch[7:9], kl_out))
+
     def update(self):
         coef = self.gradient_penalty_coef()
-        if self.graph_update and self.storage is not None and str(self.device).startswith("cuda"):
-            if self._graphed is None:
-                self._graphed = _GraphedStepLCP(self)
-            self._graphed.coef.fill_(coef)
-            out = self._graphed.update()
-            if self.fused is not None:  # graph replays write the parameters without bumping their versions
-                self.fused.refresh()
-            self.update_counter()
-            out["gradient_penalty_coef"] = coef
-            return out
-        mean_value_loss = torch.zeros((), device=self.device)
-        mean_surrogate_loss = torch.zeros((), device=self.device)
-        mean_grad_penalty_loss = torch.zeros((), device=self.device)
-        generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
-        params = list(self.policy.parameters())
-        flat = self.flat_grads()
-        flat.bind()
-        for (obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
-             old_actions_log_prob_batch, old_mu_batch, old_sigma_batch, hid_states_batch, masks_batch) in generator:
-            if self._use_fused_penalty(obs_batch, critic_obs_batch):
-                loss, stats, pen = self._fused_lcp_loss(
-                    obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
-                    old_actions_log_prob_batch, old_mu_batch, old_sigma_batch, coef)
-                surrogate_loss, value_loss = stats[0], stats[1]
-                self._adapt_learning_rate_kl(stats[2])
-            else:
-                loss, surrogate_loss, value_loss, pen, mu_batch, sigma_batch = self._torch_lcp_loss(
-                    obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
-                    old_actions_log_prob_batch, coef)
-                self._adapt_learning_rate(mu_batch, sigma_batch, old_mu_batch, old_sigma_batch)
-            self.optimizer.zero_grad(set_to_none=False)  # (in place: the views of the flat buffer stay bound)
-            if not self._grads_checked:
-                flat = self._check_all_grads(loss, params)
-                flat.bind()
-            loss.backward()
-            gdist.allreduce_grads(params, flat)
-            _fadam.clip_grad_norm_(self.optimizer, params, self.max_grad_norm)
-            self.optimizer.step()
-            mean_value_loss += value_loss.detach()
-            mean_surrogate_loss += surrogate_loss.detach()
-            mean_grad_penalty_loss += pen.detach()
-        num_updates = self.num_learning_epochs * self.num_mini_batches
-        self.storage.clear()
+        out = super().update()
         self.update_counter()
-        return {
-            "value_function": float(mean_value_loss) / num_updates,
-            "surrogate": float(mean_surrogate_loss) / num_updates,
-            "grad_penalty": float(mean_grad_penalty_loss) / num_updates,
-            "gradient_penalty_coef": coef,
-        }
+        out["gradient_penalty_coef"] = coef
+        return out
 
 
 class _GraphedStepLCP(_GraphedStep):
     """PPOLCP.update's mini-batch step as hipGraph replays (ppo.py _GraphedStep).  Segment A adds coef * P to the PPO
-    loss, with the coefficient in a device scalar (`coef`) that PPOLCP.update fills before each update's replays, so
-    the schedule moves without a re-capture; the update's sum of P accumulates beside the surrogate and value sums.
-    Segment B is the base class's."""
+    loss, with the coefficient in a device scalar (`coef`) filled before each update's replays, so the schedule
+    moves without a re-capture."""
 
     def __init__(self, alg: "PPOLCP"):
         super().__init__(alg)
-        self.acc = torch.zeros(3, device=alg.device)  # the update's sums of the surrogate, value and penalty means
         self.coef = torch.zeros((), device=alg.device)
 
-    def _seg_a(self, idx=None):
-        alg = self.alg
-        obs, priv, act, val, adv, ret, logp, mu, sig = self._gather(self.idx if idx is None else idx)
-        obs, priv = obs.float(), priv.float()
-        if alg._use_fused_penalty(obs, priv):
-            loss, _, pen = alg._fused_lcp_loss(obs, priv, act, val, adv, ret, logp, mu, sig, self.coef,
-                                               acc=self.acc[:2],
-                                               kl_out=self.flat.extra[:1] if self._adaptive() else None)
-            self.acc[2:].add_(pen.detach())
-            self._backward(loss)
-            return
-        loss, surrogate_loss, value_loss, pen, mu_b, sigma_b = alg._torch_lcp_loss(obs, priv, act, val, adv, ret, logp,
-                                                                                   self.coef)
-        if self._adaptive():
-            with torch.no_grad():
-                kl = torch.sum(torch.log(sigma_b / sig + 1.0e-5)
-                               + (torch.square(sig) + torch.square(mu - mu_b)) / (2.0 * torch.square(sigma_b)) - 0.5,
-                               axis=-1)
-                self.flat.extra[0].copy_(torch.mean(kl))
-        self.acc.add_(torch.stack([surrogate_loss.detach(), value_loss.detach(), pen.detach()]))
-        self._backward(loss)
+    def update(self):
+        self.coef.fill_(self.alg.gradient_penalty_coef())
+        return super().update()
 
-    def _stats(self, num_updates):
-        sl, vl, pl = self.acc.tolist()
-        return {"value_function": vl / num_updates, "surrogate": sl / num_updates, "grad_penalty": pl / num_updates}
+
+PPOLCP.graphed_step_cls = _GraphedStepLCP
