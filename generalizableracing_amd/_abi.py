@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 8
+GR_ABI_VERSION = 9
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -249,12 +249,22 @@ class GrTransitionArgs(C.Structure):
                                   "out_sigma")]
 
 
+class GrStemImage(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("ld", C.c_int64), ("off", C.c_int64), ("rows", C.c_void_p), ("nimg", C.c_int32),
+                ("pix", C.c_void_p), ("na", C.c_int32), ("nb", C.c_int32), ("conv_w", C.c_void_p), ("c", C.c_int32)]
+
+
+class GrBnAct(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("stats", C.c_void_p), ("c", C.c_int32), ("eps", C.c_float),
+                ("act", C.c_int32), ("slope", C.c_float)]
+
+
 # the mirror of each struct of include/gr.h (tests/test_abi.py checks every size and field offset against the header)
 STRUCTS = {"gr_config": GrConfig, "gr_buffers": GrBuffers, "gr_camera_config": GrCameraConfig,
            "gr_camera_buffers": GrCameraBuffers, "gr_obstacles": GrObstacles, "gr_policy_net": GrPolicyNet,
            "gr_policy_args": GrPolicyArgs, "gr_mlp_net": GrMlpNet, "gr_mlp_args": GrMlpArgs,
            "gr_ppo_loss_args": GrPpoLossArgs, "gr_adam_segment": GrAdamSegment, "gr_adam_args": GrAdamArgs,
-           "gr_transition_args": GrTransitionArgs}
+           "gr_transition_args": GrTransitionArgs, "gr_stem_image": GrStemImage, "gr_bn_act": GrBnAct}
 
 
 GR_POLICY_ACT_LRELU, GR_POLICY_ACT_ELU = 0, 1
@@ -273,8 +283,8 @@ STATUS_TEXT = {GR_STATUS_OBST_WAIT_TIMEOUT: "a physics wave gave up waiting for 
 # every entry point of include/gr.h: name -> (restype, argtypes).  tests/test_abi.py parses the header's prototypes and
 # compares them with this table parameter by parameter.
 vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
-# the image-side arguments the stem entry points share (img, ld, offset, rows, nimg, pix, na, nb, conv w, c, BN w, BN b)
-_IMG = [vp, i64, i64, vp, i32, vp, i32, i32, vp, i32, vp, vp]
+# what every stem entry point starts with: the image side and the BatchNorm + activation
+_STEM = [C.POINTER(GrStemImage), C.POINTER(GrBnAct)]
 SIGNATURES = {
     "gr_abi_version": (C.c_int, []),
     "gr_config_default": (C.c_int, [C.POINTER(GrConfig)]),
@@ -288,7 +298,6 @@ SIGNATURES = {
     "gr_bytes_per_env_step": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "gr_bind_tracks": (C.c_int, [vp, vp, vp]),
     "gr_bind_obstacles": (C.c_int, [vp, C.POINTER(GrObstacles)]),
-    "gr_swap_terrain": (C.c_int, [vp, vp, vp, vp, C.POINTER(GrObstacles), C.POINTER(GrObstacles), vp]),
     "gr_terrain_reserve": (C.c_int, [vp, i32, i32, i32]),
     "gr_terrain_stage": (C.c_int, [vp, vp, vp, C.POINTER(GrObstacles), vp]),
     "gr_terrain_commit": (C.c_int, [vp, vp]),
@@ -336,8 +345,8 @@ SIGNATURES = {
     "gr_gae": (C.c_int, [i64, i32, f32, f32, vp, vp, vp, vp, i64, vp, vp, vp]),
     "gr_l2c2_mix": (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
     "gr_l2c2_mix_rows": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp]),
-    "gr_tsgemm_bnact": (C.c_int, [vp, i64, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, f32, vp]),
-    "gr_patch_wgrad_bnact": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, i32, f32, vp]),
+    "gr_tsgemm_bnact": (C.c_int, [vp, i64, vp, vp, i64, i64, i32, i32, C.POINTER(GrBnAct), vp]),
+    "gr_patch_wgrad_bnact": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, C.POINTER(GrBnAct), vp]),
     "gr_bn_stats": (C.c_int, [vp, i64, i32, f32, vp, vp, vp]),
     "gr_adam_clip": (C.c_int, [C.POINTER(GrAdamArgs), f32, vp, vp]),
     "gr_adam_step": (C.c_int, [C.POINTER(GrAdamArgs), vp]),
@@ -367,16 +376,16 @@ SIGNATURES = {
     "gr_bn_act_forward": (C.c_int, [vp, i64, i32, vp, vp, f32, i32, f32, vp, vp, vp, vp]),
     "gr_bn_act_backward": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp]),
     "gr_stem1_scratch_doubles": (i64, [i32, i32, i32]),
-    "gr_stem1_forward": (C.c_int, _IMG + [f32, i32, f32, vp, i64, vp, vp, vp]),
-    "gr_stem1_backward": (C.c_int, _IMG + [vp, i32, f32, vp, i64, vp, vp, vp, vp, vp]),
+    "gr_stem1_forward": (C.c_int, _STEM + [vp, i64, vp, vp]),
+    "gr_stem1_backward": (C.c_int, _STEM + [vp, i64, vp, vp, vp, vp, vp]),
     "gr_patch_wgrad_floats": (i64, [i64, i32, i32]),
     "gr_patch_wgrad": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, vp]),
     "gr_bn_running_update": (C.c_int, [vp, vp, vp, vp, i32, f32, f32, i32, i32, vp]),
     "gr_tsgemm": (C.c_int, [vp, i64, vp, i32, vp, i64, i64, i32, i32, vp]),
-    "gr_stem12_forward": (C.c_int, _IMG + [f32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
-    "gr_stem12_backward": (C.c_int, _IMG + [vp, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "gr_stem12_forward": (C.c_int, _STEM + [vp, i32, vp, vp, vp, vp, vp]),
+    "gr_stem12_backward": (C.c_int, _STEM + [vp, i32, vp, vp, vp, vp, vp, vp]),
     "gr_stem12_backward_w2_scratch_doubles": (i64, [i32]),
-    "gr_stem12_backward_w2": (C.c_int, _IMG + [vp, vp, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "gr_stem12_backward_w2": (C.c_int, _STEM + [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -77,6 +77,7 @@ int hip_fail(gr_ctx* c, hipError_t e, const char* what) {
   return fail(c, GR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+bool act_ok(int32_t act) { return act == GR_POLICY_ACT_LRELU || act == GR_POLICY_ACT_ELU; }
 
 // device copy of the constants, made on first device use (gr_create stays host-only)
 int ensure_dev(gr_ctx* c, const char* what) {
@@ -461,33 +462,6 @@ int gr_bind_obstacles(gr_ctx* c, const gr_obstacles* o) {
   if (rc != GR_OK) return rc;
   e = hipDeviceSynchronize();
   return e == hipSuccess ? GR_OK : hip_fail(c, e, "gr_bind_obstacles: sync");
-}
-
-int gr_swap_terrain(gr_ctx* c, const float* gates, const float* tracks, const float* tracks_host,
-                    const gr_obstacles* obst, const gr_obstacles* obst_host, void* stream) {
-  if (!c || !gates || !tracks || !tracks_host) return fail(c, GR_ERR_ARG, "gr_swap_terrain: null pointer");
-  int rc = check_track_records(c, tracks_host, "gr_swap_terrain");
-  if (rc != GR_OK) return rc;
-  if (obst) {
-    if (!obst_host || !obst_host->counts || !obst_host->grid_f || !obst_host->grid_i || !obst_host->cells)
-      return fail(c, GR_ERR_ARG, "gr_swap_terrain: obstacles need their host index arrays");
-    rc = check_obstacle_arrays(c, obst, "gr_swap_terrain");
-    if (rc != GR_OK) return rc;
-    if (obst_host->num_cells != obst->num_cells || obst_host->num_items != obst->num_items ||
-        obst_host->max_obstacles != obst->max_obstacles)
-      return fail(c, GR_ERR_ARG, "gr_swap_terrain: host and device obstacle sizes differ");
-    rc = check_obstacles(c, obst, obst_host->counts, obst_host->grid_f, obst_host->grid_i, obst_host->cells,
-                         "gr_swap_terrain");
-    if (rc != GR_OK) return rc;
-  }
-  const hipStream_t s = (hipStream_t)stream;
-  rc = pack_tracks(c, gates, tracks, s, "gr_swap_terrain: pack");
-  if (rc != GR_OK) return rc;
-  if (!obst) {
-    unbind_obstacles(c);
-    return GR_OK;
-  }
-  return attach_obstacles(c, obst, obst_host->grid_f[2], obst_host->grid_f[3], s, "gr_swap_terrain: clear hints");
 }
 
 static size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }
@@ -909,8 +883,7 @@ int gr_camera_bytes_per_env(const gr_ctx* c, int64_t* render_bytes, int64_t* reu
 
 int gr_policy_forward(const gr_policy_args* a, void* stream) {
   if (!a || a->num_envs <= 0 || (a->hidden != 128 && a->hidden != 256) ||
-      (a->activation != GR_POLICY_ACT_LRELU && a->activation != GR_POLICY_ACT_ELU) ||
-      (a->precision != GR_POLICY_BF16 && a->precision != GR_POLICY_FP32))
+      !act_ok(a->activation) || (a->precision != GR_POLICY_BF16 && a->precision != GR_POLICY_FP32))
     return GR_ERR_ARG;
   // net[1].obs == NULL: actor only (rollouts without a value estimate: play, the env-only rate)
   const int nets = a->net[1].obs ? 2 : 1;
@@ -938,7 +911,7 @@ int64_t gr_bn_scratch_doubles(int64_t m, int32_t c) {
 int gr_bn_act_forward(const float* x, int64_t m, int32_t c, const float* w, const float* b, float eps, int32_t act,
                       float slope, float* y, float* stats, double* part, void* stream) {
   if (!bn_shape_ok(m, c) || !x || !w || !b || !y || !stats || !part || !aligned16(x) || !aligned16(y) ||
-      !aligned16(w) || !aligned16(b) || !aligned16(stats) || (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU))
+      !aligned16(w) || !aligned16(b) || !aligned16(stats) || !act_ok(act))
     return GR_ERR_ARG;
   const hipError_t e = gr::launch_bn_forward(x, m, c, w, b, eps, act, slope, y, stats, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
@@ -957,29 +930,35 @@ int gr_bn_act_backward(const float* x, const float* gy, int64_t m, int32_t c, co
                        const float* stats, int32_t act, float slope, float* gx, float* gw, float* gb, double* part,
                        void* stream) {
   if (!bn_shape_ok(m, c) || !x || !gy || !w || !b || !stats || !gx || !gw || !gb || !part || !aligned16(x) ||
-      !aligned16(gy) || !aligned16(gx) || !aligned16(w) || !aligned16(b) || !aligned16(stats) ||
-      (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU))
+      !aligned16(gy) || !aligned16(gx) || !aligned16(w) || !aligned16(b) || !aligned16(stats) || !act_ok(act))
     return GR_ERR_ARG;
   const hipError_t e =
       gr::launch_bn_backward(x, gy, m, c, w, b, stats, act, slope, gx, gw, gb, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
-static bool stem1_args_ok(const float* obs, int32_t nimg, const int16_t* pix, int32_t na, int32_t nb,
-                          const float* conv_w, int32_t c, const float* bn_w, const float* bn_b) {
-  return obs && pix && conv_w && bn_w && bn_b && nimg >= 1 && na >= 1 && nb >= 0 && na + nb <= 1024 &&
-         (int64_t)nimg * (na + nb) < (int64_t)1 << 31 && bn_shape_ok(1, c) && aligned16(bn_w) && aligned16(bn_b);
+// the image and BatchNorm sides every stem entry point takes: non-null, in range, the BatchNorm's buffers 16-byte aligned
+static bool stem1_args_ok(const gr_stem_image* i, const gr_bn_act* bn) {
+  return i && bn && i->obs && i->pix && i->conv_w && bn->w && bn->b && bn->stats && i->nimg >= 1 && i->na >= 1 &&
+         i->nb >= 0 && i->na + i->nb <= 1024 && (int64_t)i->nimg * (i->na + i->nb) < (int64_t)1 << 31 &&
+         bn_shape_ok(1, i->c) && bn->c == i->c && aligned16(bn->w) && aligned16(bn->b) && aligned16(bn->stats) &&
+         act_ok(bn->act);
 }
-static gr::Stem1 stem1_of(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                          int32_t nb, const float* conv_w, int32_t c, int64_t rows_out) {
+static gr::Stem1 stem1_of(const gr_stem_image* i, int64_t rows_out) {
   gr::Stem1 s;
-  s.obs = obs; s.ld = ld; s.off = off; s.nimg = nimg; s.na = na; s.nbt = nb;
-  s.rows = reinterpret_cast<const long long*>(rows);
-  s.pix = reinterpret_cast<const short*>(pix); s.w = conv_w; s.c = c; s.rows_out = rows_out;
+  s.obs = i->obs; s.ld = i->ld; s.off = i->off; s.nimg = i->nimg; s.na = i->na; s.nbt = i->nb;
+  s.rows = reinterpret_cast<const long long*>(i->rows);
+  s.pix = reinterpret_cast<const short*>(i->pix); s.w = i->conv_w; s.c = i->c; s.rows_out = rows_out;
   return s;
 }
-static bool stem1_rows_ok(int32_t nimg, int32_t na, int32_t nb, int64_t rows_out) {
-  return rows_out >= 1 && rows_out <= (int64_t)nimg * (na + nb);
+static bool stem1_rows_ok(const gr_stem_image* i, int64_t rows_out) {
+  return rows_out >= 1 && rows_out <= (int64_t)i->nimg * (i->na + i->nb);
+}
+// ... and conv2 on the table-a rows: 16 channels, na = 9 n2, conv2's 32-wide rows within 32-bit offsets, the forward's
+// moments 8-byte aligned doubles (or null)
+static bool stem12_args_ok(const gr_stem_image* i, const gr_bn_act* bn, int32_t n2, const void* moments) {
+  return stem1_args_ok(i, bn) && i->c == 16 && n2 >= 1 && i->na == 9 * n2 &&
+         (int64_t)i->nimg * n2 * 32 < (int64_t)1 << 31 && !(reinterpret_cast<uintptr_t>(moments) & 7u);
 }
 
 int64_t gr_stem1_scratch_doubles(int32_t nimg, int32_t rows_per_img, int32_t c) {
@@ -987,28 +966,19 @@ int64_t gr_stem1_scratch_doubles(int32_t nimg, int32_t rows_per_img, int32_t c) 
   return gr::stem1_scratch_doubles(nimg, rows_per_img, c);
 }
 
-int gr_stem1_forward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                     int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b, float eps,
-                     int32_t act, float slope, float* y, int64_t y_rows, float* stats, double* part, void* stream) {
-  if (!stem1_args_ok(obs, nimg, pix, na, nb, conv_w, c, bn_w, bn_b) || !y || !stats || !part || !aligned16(y) ||
-      !aligned16(stats) || (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU) ||
-      !stem1_rows_ok(nimg, na, nb, y_rows))
-    return GR_ERR_ARG;
-  const gr::Stem1 s = stem1_of(obs, ld, off, rows, nimg, pix, na, nb, conv_w, c, y_rows);
-  const hipError_t e = gr::launch_stem1_forward(s, bn_w, bn_b, eps, act, slope, y, stats, part, (hipStream_t)stream);
+int gr_stem1_forward(const gr_stem_image* img, const gr_bn_act* bn, float* y, int64_t y_rows, double* part,
+                     void* stream) {
+  if (!stem1_args_ok(img, bn) || !y || !part || !aligned16(y) || !stem1_rows_ok(img, y_rows)) return GR_ERR_ARG;
+  const hipError_t e = gr::launch_stem1_forward(stem1_of(img, y_rows), *bn, y, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
-int gr_stem1_backward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                      int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                      const float* stats, int32_t act, float slope, const float* gy, int64_t gy_rows, float* g_conv_w,
+int gr_stem1_backward(const gr_stem_image* img, const gr_bn_act* bn, const float* gy, int64_t gy_rows, float* g_conv_w,
                       float* g_bn_w, float* g_bn_b, double* part, void* stream) {
-  if (!stem1_args_ok(obs, nimg, pix, na, nb, conv_w, c, bn_w, bn_b) || !stats || !gy || !g_conv_w || !g_bn_w ||
-      !g_bn_b || !part || !aligned16(gy) || !aligned16(stats) || (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU) ||
-      !stem1_rows_ok(nimg, na, nb, gy_rows))
+  if (!stem1_args_ok(img, bn) || !gy || !g_conv_w || !g_bn_w || !g_bn_b || !part || !aligned16(gy) ||
+      !stem1_rows_ok(img, gy_rows))
     return GR_ERR_ARG;
-  const gr::Stem1 s = stem1_of(obs, ld, off, rows, nimg, pix, na, nb, conv_w, c, gy_rows);
-  const hipError_t e = gr::launch_stem1_backward(s, bn_w, bn_b, stats, act, slope, gy, g_conv_w, g_bn_w, g_bn_b, part,
+  const hipError_t e = gr::launch_stem1_backward(stem1_of(img, gy_rows), *bn, gy, g_conv_w, g_bn_w, g_bn_b, part,
                                                  (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
@@ -1024,20 +994,17 @@ int gr_tsgemm(const float* a, int64_t lda, const float* b, int32_t b_nk, float* 
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
-static bool bnact_of(int32_t bn_c, const float* stats, const float* bn_w, const float* bn_b, int32_t act, float slope,
-                     gr::BnAct* p) {
-  if (!stats || !bn_w || !bn_b || !bn_shape_ok(1, bn_c) || (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU))
-    return false;
-  p->stats = stats; p->w = bn_w; p->b = bn_b; p->c = bn_c; p->act = act; p->slope = slope;
+static bool bnact_of(const gr_bn_act* bn, gr::BnAct* p) {
+  if (!bn || !bn->stats || !bn->w || !bn->b || !bn_shape_ok(1, bn->c) || !act_ok(bn->act)) return false;
+  p->stats = bn->stats; p->w = bn->w; p->b = bn->b; p->c = bn->c; p->act = bn->act; p->slope = bn->slope;
   return true;
 }
 
 int gr_tsgemm_bnact(const float* z, int64_t lda, const float* b, float* c, int64_t ldc, int64_t m, int32_t k, int32_t n,
-                    int32_t bn_c, const float* stats, const float* bn_w, const float* bn_b, int32_t act, float slope,
-                    void* stream) {
+                    const gr_bn_act* bn, void* stream) {
   gr::BnAct p;
-  if (!z || !b || !c || m < 0 || k != 128 || n != 64 || lda < k || ldc < n || ((uintptr_t)z & 3) || bn_c != 32 ||
-      !bnact_of(bn_c, stats, bn_w, bn_b, act, slope, &p) || m * (lda > ldc ? lda : ldc) >= ((int64_t)1 << 40))
+  if (!z || !b || !c || m < 0 || k != 128 || n != 64 || lda < k || ldc < n || ((uintptr_t)z & 3) || !bnact_of(bn, &p) ||
+      p.c != 32 || m * (lda > ldc ? lda : ldc) >= ((int64_t)1 << 40))
     return GR_ERR_ARG;
   if (m == 0) return GR_OK;
   const hipError_t e = gr::launch_tsgemm(z, (long long)lda, b, true, c, (long long)ldc, (long long)m, k, n, &p,
@@ -1068,46 +1035,33 @@ int gr_patch_wgrad(const float* x, int64_t ld, const float* gy, int64_t m, int32
 }
 
 int gr_patch_wgrad_bnact(const float* z, int64_t ld, const float* gy, int64_t m, int32_t n, int32_t k, float* part,
-                         float* gw, int32_t bn_c, const float* stats, const float* bn_w, const float* bn_b, int32_t act,
-                         float slope, void* stream) {
+                         float* gw, const gr_bn_act* bn, void* stream) {
   gr::BnAct p;
   if (!z || !gy || !part || !gw || m < 1 || n % 64 || gr::patch_wgrad_blocks(m, n, k) == 0 || ld < k ||
-      !aligned16(gy) || ((uintptr_t)z & 3) || bn_c % 8 || 128 % bn_c || !bnact_of(bn_c, stats, bn_w, bn_b, act, slope, &p) ||
-      m * ld >= ((int64_t)1 << 40))
+      !aligned16(gy) || ((uintptr_t)z & 3) || !bnact_of(bn, &p) || p.c % 8 || 128 % p.c || m * ld >= ((int64_t)1 << 40))
     return GR_ERR_ARG;
   const hipError_t e = gr::launch_patch_wgrad(z, (long long)ld, gy, (long long)m, n, k, part, gw, &p,
                                               (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
-int gr_stem12_forward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                      int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b, float eps,
-                      int32_t act, float slope, const float* w2f, int32_t n2, float* y, float* z2, float* stats,
+int gr_stem12_forward(const gr_stem_image* img, const gr_bn_act* bn, const float* w2f, int32_t n2, float* y, float* z2,
                       double* moments, double* part, void* stream) {
-  if (!stem1_args_ok(obs, nimg, pix, na, nb, conv_w, c, bn_w, bn_b) || c != 16 || !w2f || !z2 || !stats ||
-      !part || !aligned16(w2f) || (y && !aligned16(y)) || !aligned16(z2) || !aligned16(stats) ||
-      (reinterpret_cast<uintptr_t>(moments) & 7u) ||
-      (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU) || n2 < 1 || na != 9 * n2 ||
-      (int64_t)nimg * n2 * 32 >= (int64_t)1 << 31)
+  if (!stem12_args_ok(img, bn, n2, moments) || !w2f || !z2 || !part || !aligned16(w2f) || (y && !aligned16(y)) ||
+      !aligned16(z2))
     return GR_ERR_ARG;
-  const gr::Stem1 s = stem1_of(obs, ld, off, rows, nimg, pix, na, nb, conv_w, c, (int64_t)nimg * na);
-  const hipError_t e = gr::launch_stem12_forward(s, bn_w, bn_b, eps, act, slope, w2f, n2, y, z2, stats, moments,
-                                                 part, (hipStream_t)stream);
+  const hipError_t e = gr::launch_stem12_forward(stem1_of(img, (int64_t)img->nimg * img->na), *bn, w2f, n2, y, z2,
+                                                 moments, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
-int gr_stem12_backward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                       int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                       const float* stats, int32_t act, float slope, const float* gz2, int32_t n2, const float* w2t,
+int gr_stem12_backward(const gr_stem_image* img, const gr_bn_act* bn, const float* gz2, int32_t n2, const float* w2t,
                        float* g_conv_w, float* g_bn_w, float* g_bn_b, double* part, void* stream) {
-  if (!stem1_args_ok(obs, nimg, pix, na, nb, conv_w, c, bn_w, bn_b) || c != 16 || !stats || !gz2 || !w2t ||
-      !g_conv_w || !g_bn_w || !g_bn_b || !part || !aligned16(gz2) || !aligned16(w2t) || !aligned16(stats) ||
-      (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU) || n2 < 1 || na != 9 * n2 ||
-      (int64_t)nimg * n2 * 32 >= (int64_t)1 << 31)
+  if (!stem12_args_ok(img, bn, n2, nullptr) || !gz2 || !w2t || !g_conv_w || !g_bn_w || !g_bn_b || !part ||
+      !aligned16(gz2) || !aligned16(w2t))
     return GR_ERR_ARG;
-  const gr::Stem1 s = stem1_of(obs, ld, off, rows, nimg, pix, na, nb, conv_w, c, (int64_t)nimg * na);
-  const hipError_t e = gr::launch_stem12_backward(s, bn_w, bn_b, stats, act, slope, gz2, n2, w2t, g_conv_w, g_bn_w,
-                                                  g_bn_b, part, (hipStream_t)stream);
+  const hipError_t e = gr::launch_stem12_backward(stem1_of(img, (int64_t)img->nimg * img->na), *bn, gz2, n2, w2t,
+                                                  g_conv_w, g_bn_w, g_bn_b, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
@@ -1115,20 +1069,15 @@ int64_t gr_stem12_backward_w2_scratch_doubles(int32_t nimg) {
   return nimg < 1 ? GR_ERR_ARG : (int64_t)gr::stem12w_scratch_doubles(nimg);
 }
 
-int gr_stem12_backward_w2(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix,
-                          int32_t na, int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                          const float* stats, const double* moments, int32_t act, float slope, const float* gz2,
+int gr_stem12_backward_w2(const gr_stem_image* img, const gr_bn_act* bn, const double* moments, const float* gz2,
                           int32_t n2, const float* w2t, float* g_conv_w, float* g_bn_w, float* g_bn_b, float* g_w2,
                           double* part, void* stream) {
-  if (!stem1_args_ok(obs, nimg, pix, na, nb, conv_w, c, bn_w, bn_b) || c != 16 || !stats || !gz2 || !w2t ||
-      !g_conv_w || !g_bn_w || !g_bn_b || !g_w2 || !part || !aligned16(gz2) || !aligned16(w2t) || !aligned16(stats) ||
-      (reinterpret_cast<uintptr_t>(moments) & 7u) ||
-      (act != GR_POLICY_ACT_LRELU && act != GR_POLICY_ACT_ELU) || !gr::stem12w_covers(n2) || na != 9 * n2 ||
-      (int64_t)nimg * n2 * 32 >= (int64_t)1 << 31)
+  if (!stem12_args_ok(img, bn, n2, moments) || !gr::stem12w_covers(n2) || !gz2 || !w2t || !g_conv_w || !g_bn_w ||
+      !g_bn_b || !g_w2 || !part || !aligned16(gz2) || !aligned16(w2t))
     return GR_ERR_ARG;
-  const gr::Stem1 s = stem1_of(obs, ld, off, rows, nimg, pix, na, nb, conv_w, c, (int64_t)nimg * na);
-  const hipError_t e = gr::launch_stem12_backward_w2(s, bn_w, bn_b, stats, moments, act, slope, gz2, n2, w2t, g_conv_w,
-                                                     g_bn_w, g_bn_b, g_w2, part, (hipStream_t)stream);
+  const hipError_t e =
+      gr::launch_stem12_backward_w2(stem1_of(img, (int64_t)img->nimg * img->na), *bn, moments, gz2, n2, w2t, g_conv_w,
+                                    g_bn_w, g_bn_b, g_w2, part, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 

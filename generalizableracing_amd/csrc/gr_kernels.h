@@ -99,7 +99,7 @@ hipError_t launch_camera(const CamArgs& a, hipStream_t s);
 hipError_t launch_policy(const gr_policy_args& a, hipStream_t s);  // gr_policy.hip
 hipError_t launch_policy_f32(const gr_policy_args& a, hipStream_t s);  // gr_policy_f32.hip
 int bn_scratch_doubles(long long m, int c);                                                // gr_bn.hip
-// the stem's first block from the image (gr_bn.hip): image b at obs + b * ld + off; rows nimg x na from
+// the stem's first block from the image (gr_stem.hip): image b at obs + b * ld + off; rows nimg x na from
 // table a, then nimg x nbt from table b; pix [(na + nbt) * 9]; conv weight w [c][9]
 struct Stem1 {
   const float* obs;
@@ -112,28 +112,26 @@ struct Stem1 {
   long long rows_out;  // rows of y / gy that exist: the forward stores rows [0, rows_out), the backward reads the
                        // gradient of those rows and takes the rest (cells no later layer reads) as zero
 };
+// the launchers below take the image as a Stem1 and the BatchNorm + activation as the ABI's gr_bn_act (forwards write
+// bn.stats, backwards read it); `part`: stem1_scratch_doubles doubles (stem12w_scratch_doubles for _backward_w2)
 long long stem1_scratch_doubles(int nimg, int rows_per_img, int c);
-hipError_t launch_stem1_forward(const Stem1& s, const float* bw, const float* bb, float eps, int act, float slope,
-                                float* y, float* stats, double* part, hipStream_t st);
-hipError_t launch_stem1_backward(const Stem1& s, const float* bw, const float* bb, const float* stats, int act,
-                                 float slope, const float* gy, float* gconv, float* gbw, float* gbb, double* part,
-                                 hipStream_t st);
-// the first block's forward with conv2 (16 -> 32, 3x3 / 3) fused into its apply pass: y1 and z2 (gr_bn.hip stem12f_kernel)
-hipError_t launch_stem12_forward(const Stem1& s, const float* bw, const float* bb, float eps, int act, float slope,
-                                 const float* w2f, int n2, float* y, float* z2, float* stats, double* moments,
-                                 double* part, hipStream_t st);
-// ... and with conv2's weight gradient gw2 [32][144] too (position-major waves, y1 recomputed: gr_bn.hip stem12w_kernel;
+hipError_t launch_stem1_forward(const Stem1& s, const gr_bn_act& bn, float* y, double* part, hipStream_t st);
+hipError_t launch_stem1_backward(const Stem1& s, const gr_bn_act& bn, const float* gy, float* gconv, float* gbw,
+                                 float* gbb, double* part, hipStream_t st);
+// the first block's forward with conv2 (16 -> 32, 3x3 / 3) fused into its apply pass: y1 and z2 (stem12f_kernel), or z2
+// alone when y is null and n2 <= 80 (stem12g_kernel)
+hipError_t launch_stem12_forward(const Stem1& s, const gr_bn_act& bn, const float* w2f, int n2, float* y, float* z2,
+                                 double* moments, double* part, hipStream_t st);
+// the backward with conv2's input gradient formed inside the passes (C = 16, na = 9 n2; stem12b_kernel)
+hipError_t launch_stem12_backward(const Stem1& s, const gr_bn_act& bn, const float* gz2, int n2, const float* w2t,
+                                  float* gconv, float* gbw, float* gbb, double* part, hipStream_t st);
+// ... and with conv2's weight gradient gw2 [32][144] too (position-major waves, y1 recomputed: stem12w_kernel;
 // n2 <= 80), so the forward needs to store no y1
 long long stem12w_scratch_doubles(int nimg);
 bool stem12w_covers(int n2);
-hipError_t launch_stem12_backward_w2(const Stem1& s, const float* bw, const float* bb, const float* stats,
-                                     const double* moments, int act, float slope, const float* gz2, int n2,
-                                     const float* w2t, float* gconv, float* gbw, float* gbb, float* gw2, double* part,
-                                     hipStream_t st);
-// the same backward with conv2's input gradient formed inside the passes (C = 16, na = 9 n2; gr_bn.hip stem12b_kernel)
-hipError_t launch_stem12_backward(const Stem1& s, const float* bw, const float* bb, const float* stats, int act,
-                                  float slope, const float* gz2, int n2, const float* w2t, float* gconv, float* gbw,
-                                  float* gbb, double* part, hipStream_t st);
+hipError_t launch_stem12_backward_w2(const Stem1& s, const gr_bn_act& bn, const double* moments, const float* gz2,
+                                     int n2, const float* w2t, float* gconv, float* gbw, float* gbb, float* gw2,
+                                     double* part, hipStream_t st);
 hipError_t launch_bn_running_update(float* rm, float* rv, long long* nbt, const float* stats, int c, float keep,
                                     float momentum, int uses, int count, hipStream_t s);
 hipError_t launch_bn_forward(const float* x, long long m, int c, const float* w, const float* b, float eps, int act,

@@ -5,7 +5,7 @@
 // uploaded ahead into the context's staging block (gr_terrain_stage, on a side stream, while the env stepped); here,
 // in one launch on the env's stream, with arguments that never change (so the interval step is graph-capturable):
 //   1. the packed gate table: [track][max_gates * GR_GATE_FLOATS | GR_TRACK_FLOATS] from the staged gates and
-//      track records (what pack_tracks' two 2-D copies do for gr_bind_tracks / gr_swap_terrain);
+//      track records (what pack_tracks' two 2-D copies do for gr_bind_tracks);
 //   2. the obstacle block [records | counts | grid_f | grid_i | cells | items] staging -> live, through the last
 //      staged item (the extent is the staged header's first word: the generation's item count varies);
 //   3. the per-env obstacle hints (state plane GR_P_OHINT) cleared: they index the previous generation's cells.

@@ -686,7 +686,7 @@ class RacingEnv:
         if self.camera is None:
             # the reset's own observation (discarded by the reference: the step computes them again) goes to a scratch
             # output set, so the runner's held set is never written and nothing is saved / restored: the interval step
-            # is gr_swap_terrain + gr_reset(all) + gr_observe on the stream
+            # is gr_terrain_commit + gr_reset(all) + gr_observe on the stream
             scratch = self._scratch_set
             if scratch is None:  # (a direct call on an env built without an interval)
                 scratch = self._scratch_set = self._alloc_outputs(self.num_envs, self.device)

@@ -1,5 +1,5 @@
 """Training-mode BatchNorm + activation on channels-last rows as one HIP op (libgr.so gr_bn_act_forward /
-gr_bn_act_backward, csrc/gr_bn.hip).
+gr_bn_act_backward, csrc/gr_bn.hip; the stem's first block from the image: csrc/gr_stem.hip).
 
 The vision stem (rsl_rl/vision_actor_critic.py, reference standalone/rsl_rl/ext/modules/
 vision_actor_critic.py:43-144) evaluates Conv -> BatchNorm2d -> LeakyReLU as patch GEMMs on [rows, C]
@@ -10,6 +10,8 @@ updated exactly as F.batch_norm does (momentum, unbiased variance).  Eval-mode B
 statistics) stays on torch's op.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -96,13 +98,19 @@ def batch_norm_act(bn: nn.BatchNorm2d, act: nn.Module, x: torch.Tensor, uses: in
     return y
 
 
-def _stem_args(img, rows, pix, na, nb, w, bw, bb):
-    """(images in the batch, the image-side arguments every gr_stem1_* / gr_stem12_* entry point starts with): the image
-    rows and their stride, the batch's row indices into them (or all of them), the pixel table, the conv weight [c, 9]
-    and the BatchNorm's affine pair."""
+def _stem_args(img, rows, pix, na, nb, w):
+    """The gr_stem_image every gr_stem1_* / gr_stem12_* entry point starts with: the image rows and their stride, the
+    batch's row indices into them (or all of them), the pixel table and the conv weight [c, 9].  It holds raw pointers:
+    the caller keeps the tensors alive across the call (they are its arguments or saved tensors)."""
     nimg = img.shape[0] if rows is None else rows.numel()
-    return nimg, (img.data_ptr(), img.stride(0), 0, rows.data_ptr() if rows is not None else None, nimg,
-                  pix.data_ptr(), na, nb, w.data_ptr(), w.shape[0], bw.data_ptr(), bb.data_ptr())
+    return _abi.GrStemImage(img.data_ptr(), img.stride(0), 0, rows.data_ptr() if rows is not None else None, nimg,
+                            pix.data_ptr(), na, nb, w.data_ptr(), w.shape[0])
+
+
+def _bn_arg(w, b, stats, act, slope, eps=0.0):
+    """The gr_bn_act of an entry point: the affine pair, the statistics [4, c] (written by a forward, read by a backward
+    or a *_bnact GEMM), the activation; eps: a forward's (the others do not read it)."""
+    return _abi.GrBnAct(w.data_ptr(), b.data_ptr(), stats.data_ptr(), w.numel(), float(eps), act, float(slope))
 
 
 class _Stem1(torch.autograd.Function):
@@ -115,12 +123,14 @@ class _Stem1(torch.autograd.Function):
         c = conv_w.shape[0]
         w = conv_w.detach().reshape(c, 9).contiguous()
         bw, bb = bn_w.detach().contiguous(), bn_b.detach().contiguous()
-        nimg, image = _stem_args(img, rows, pix, na, nb, w, bw, bb)
+        image = _stem_args(img, rows, pix, na, nb, w)
+        nimg = image.nimg
         y = torch.empty(nimg * na, c, device=img.device, dtype=torch.float32)
         stats = torch.empty(4, c, device=img.device, dtype=torch.float32)
         part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, c)
-        _abi.call("gr_stem1_forward", *image, float(eps), act, float(slope), y.data_ptr(), nimg * na, stats.data_ptr(),
-                  part.data_ptr(), _abi.raw_stream(img.device))
+        bn = _bn_arg(bw, bb, stats, act, slope, eps)
+        _abi.call("gr_stem1_forward", C.byref(image), C.byref(bn), y.data_ptr(), nimg * na, part.data_ptr(),
+                  _abi.raw_stream(img.device))
         ctx.save_for_backward(img, w, bw, bb, stats)
         ctx.pix = pix  # a constant table (possibly made under inference mode): kept as an attribute
         ctx.rows = rows  # (the batch's row indices into img, or None)
@@ -134,15 +144,16 @@ class _Stem1(torch.autograd.Function):
             raise RuntimeError("the fused stem computes no gradient for the image")
         img, w, bw, bb, stats = ctx.saved_tensors
         na, nb, act, slope, wshape = ctx.args
-        nimg, image = _stem_args(img, ctx.rows, ctx.pix, na, nb, w, bw, bb)
-        c = w.shape[0]
+        image = _stem_args(img, ctx.rows, ctx.pix, na, nb, w)
+        bn = _bn_arg(bw, bb, stats, act, slope)
+        nimg, c = image.nimg, w.shape[0]
         gy = gy.contiguous()
         gconv = torch.empty(c, 9, device=img.device, dtype=torch.float32)
         gbw = torch.empty(c, device=img.device, dtype=torch.float32)
         gbb = torch.empty(c, device=img.device, dtype=torch.float32)
         part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, c)
-        _abi.call("gr_stem1_backward", *image, stats.data_ptr(), act, float(slope), gy.data_ptr(), gy.shape[0],
-                  gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), _abi.raw_stream(img.device))
+        _abi.call("gr_stem1_backward", C.byref(image), C.byref(bn), gy.data_ptr(), gy.shape[0], gconv.data_ptr(),
+                  gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), _abi.raw_stream(img.device))
         return None, gconv.view(wshape), gbw, gbb, None, None, None, None, None, None, None
 
 
@@ -172,7 +183,8 @@ class _Stem12(torch.autograd.Function):
                 keep_y=True):
         w = conv_w.detach().reshape(16, 9).contiguous()
         bw, bb = bn_w.detach().contiguous(), bn_b.detach().contiguous()
-        nimg, image = _stem_args(img, rows, pix, na, nb, w, bw, bb)
+        image = _stem_args(img, rows, pix, na, nb, w)
+        nimg = image.nimg
         # (keep_y False: no backward will run, so y1 — kept only for conv2's weight gradient — is not stored; nor when
         # that gradient is formed inside the first block's backward)
         w2_path = _w2_path(fused_forward, na)
@@ -185,17 +197,17 @@ class _Stem12(torch.autograd.Function):
         # the statistics pass's pixel moments, when the backward will take conv1's A2 / A3 sums from them
         mom = torch.empty(64 if (w2_path and STEM12_MOMENTS and backward_follows) else 0, device=img.device,
                           dtype=torch.float64)
+        bn = _bn_arg(bw, bb, stats, act, slope, eps)
         stream = _abi.raw_stream(img.device)
         if fused_forward:
             # conv2 inside the first block's apply pass: w2f[j][g][o][v] = W2[o][j * 16 + 4 g + v]
             w2f = w2d.reshape(32, 9, 4, 4).permute(1, 2, 0, 3).contiguous()
             z2 = torch.empty(nimg * (na // 9), 32, device=img.device, dtype=torch.float32)
-            _abi.call("gr_stem12_forward", *image, float(eps), act, float(slope), w2f.data_ptr(), na // 9,
-                      y.data_ptr() if keep_y else None, z2.data_ptr(), stats.data_ptr(),
-                      mom.data_ptr() if mom.numel() else None, part.data_ptr(), stream)
+            _abi.call("gr_stem12_forward", C.byref(image), C.byref(bn), w2f.data_ptr(), na // 9,
+                      y.data_ptr() if keep_y else None, z2.data_ptr(), mom.data_ptr() if mom.numel() else None,
+                      part.data_ptr(), stream)
         else:  # the first block's kernels, then conv2 as a GEMM (the A/B reference of the fused forward)
-            _abi.call("gr_stem1_forward", *image, float(eps), act, float(slope), y.data_ptr(), nimg * na,
-                      stats.data_ptr(), part.data_ptr(), stream)
+            _abi.call("gr_stem1_forward", C.byref(image), C.byref(bn), y.data_ptr(), nimg * na, part.data_ptr(), stream)
             z2 = y.view(-1, 144) @ w2d.t()
         ctx.save_for_backward(img, w, bw, bb, stats, y, w2d, mom)
         ctx.pix = pix
@@ -211,7 +223,8 @@ class _Stem12(torch.autograd.Function):
             raise RuntimeError("the fused stem computes no gradient for the image")
         img, w, bw, bb, stats, y, w2d, mom = ctx.saved_tensors
         na, nb, act, slope, wshape = ctx.args
-        nimg, image = _stem_args(img, ctx.rows, ctx.pix, na, nb, w, bw, bb)
+        image, bn = _stem_args(img, ctx.rows, ctx.pix, na, nb, w), _bn_arg(bw, bb, stats, act, slope)
+        nimg = image.nimg
         gz2 = gz2.contiguous()
         if gz2.data_ptr() % 16:
             gz2 = gz2.clone()
@@ -224,9 +237,9 @@ class _Stem12(torch.autograd.Function):
         if ctx.w2_path:  # the first block's backward with conv2's dgrad and wgrad (y1 recomputed)
             gw2 = torch.empty(32, 144, device=img.device, dtype=torch.float32)
             part = _scratch(img.device, "gr_stem12_backward_w2_scratch_doubles", nimg)
-            _abi.call("gr_stem12_backward_w2", *image, stats.data_ptr(), mom.data_ptr() if mom.numel() else None, act,
-                      float(slope), gz2.data_ptr(), na // 9, w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(),
-                      gbb.data_ptr(), gw2.data_ptr(), part.data_ptr(), stream)
+            _abi.call("gr_stem12_backward_w2", C.byref(image), C.byref(bn), mom.data_ptr() if mom.numel() else None,
+                      gz2.data_ptr(), na // 9, w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(),
+                      gw2.data_ptr(), part.data_ptr(), stream)
             if not ctx.needs_input_grad[4]:
                 gw2 = None
         else:
@@ -236,8 +249,8 @@ class _Stem12(torch.autograd.Function):
 
                 gw2 = tall_wgrad(gz2, y.view(y.shape[0] // 9, 144))
             part = _scratch(img.device, "gr_stem1_scratch_doubles", nimg, na + nb, 16)
-            _abi.call("gr_stem12_backward", *image, stats.data_ptr(), act, float(slope), gz2.data_ptr(), na // 9,
-                      w2t.data_ptr(), gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), stream)
+            _abi.call("gr_stem12_backward", C.byref(image), C.byref(bn), gz2.data_ptr(), na // 9, w2t.data_ptr(),
+                      gconv.data_ptr(), gbw.data_ptr(), gbb.data_ptr(), part.data_ptr(), stream)
         return None, gconv.view(wshape), gbw, gbb, gw2, None, None, None, None, None, None, None, None, None
 
 
@@ -258,8 +271,8 @@ class _BnActPatchGemm(torch.autograd.Function):
         bw, bb, wd = bn_w.detach().contiguous(), bn_b.detach().contiguous(), w.detach().contiguous()
         mp = m * c // k
         y = torch.empty(mp, n, device=z.device, dtype=torch.float32)
-        _abi.call("gr_tsgemm_bnact", z.data_ptr(), k, wd.data_ptr(), y.data_ptr(), n, mp, k, n, c, stats.data_ptr(),
-                  bw.data_ptr(), bb.data_ptr(), act, float(slope), _abi.raw_stream(z.device))
+        _abi.call("gr_tsgemm_bnact", z.data_ptr(), k, wd.data_ptr(), y.data_ptr(), n, mp, k, n,
+                  C.byref(_bn_arg(bw, bb, stats, act, slope)), _abi.raw_stream(z.device))
         ctx.save_for_backward(z, bw, bb, stats, wd)
         ctx.act, ctx.slope = act, slope
         ctx.mark_non_differentiable(stats)
@@ -279,7 +292,7 @@ class _BnActPatchGemm(torch.autograd.Function):
             gw = torch.empty(n, k, device=dev, dtype=torch.float32)
             wpart = torch.empty(int(_abi.load().gr_patch_wgrad_floats(mp, n, k)), device=dev, dtype=torch.float32)
             _abi.call("gr_patch_wgrad_bnact", z.data_ptr(), k, gy.data_ptr(), mp, n, k, wpart.data_ptr(), gw.data_ptr(),
-                      c, stats.data_ptr(), bw.data_ptr(), bb.data_ptr(), ctx.act, float(ctx.slope), stream)
+                      C.byref(_bn_arg(bw, bb, stats, ctx.act, ctx.slope)), stream)
         # the gradient of act(bn(z)) = gy w, then the BatchNorm + activation backward on z
         dblock = torch.empty(mp, k, device=dev, dtype=torch.float32)
         _abi.call("gr_tsgemm", gy.data_ptr(), n, w.data_ptr(), 0, dblock.data_ptr(), k, mp, n, k, stream)

@@ -39,8 +39,9 @@ extern "C" {
  * status word; gr_policy_args_size.  3: gr_stem1_* y_rows / gy_rows.  4: the gr_stem1_* / gr_stem12_* row indices
  * (`rows` after `off`).  5: gr_stem12_backward_w2 (conv2's weight gradient inside the first block's backward).
  * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward
- * 8: gr_offline_collect / gr_offline_pgd_step */
-#define GR_ABI_VERSION 8
+ * 8: gr_offline_collect / gr_offline_pgd_step.  9: gr_stem_image / gr_bn_act in place of the stem entry points' and the
+ * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit) */
+#define GR_ABI_VERSION 9
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -301,16 +302,6 @@ typedef struct gr_obstacles {
 /* obst == NULL unbinds (obstacle-free tracks).  Validates counts and the grid (host copies of
  * the small index arrays). */
 int gr_bind_obstacles(gr_ctx* ctx, const gr_obstacles* obst);
-/* Terrain swap of the periodic regeneration (EventCfg.reset_terrain -> reset_terrain_period,
- * extensions/diff.lab_tasks/diff/lab_tasks/tasks/quadcopter_diff/mdp/events.py:180-204) without a host
- * synchronisation: the new tables are validated from HOST copies (`tracks_host` [num_types*num_levels]
- * [GR_TRACK_FLOATS]; `obst_host` with the host counts / grid_f / grid_i / cells, sizes as `obst`), then, ordered on
- * `stream`, the device gate table is packed into the context's table and the obstacle hints are cleared; `obst`
- * (device arrays, caller-owned, kept alive while bound) is bound, or NULL unbinds.  Launches enqueued earlier on
- * `stream` run on the previous tables.  Same tables -> same steps as gr_bind_tracks + gr_bind_obstacles. */
-int gr_swap_terrain(gr_ctx* ctx, const float* gates, const float* tracks, const float* tracks_host,
-                    const gr_obstacles* obst, const gr_obstacles* obst_host, void* stream);
-
 /* Resident terrain: the periodic regeneration (EventCfg.reset_terrain -> reset_terrain_period, .../quadcopter_diff/
  * mdp/events.py:180-204) as a swap with fixed device addresses, so the interval step can be captured in a hipGraph.
  *   gr_terrain_reserve: the context allocates, once, the arrays the kernels read the terrain from (the packed gate
@@ -466,14 +457,36 @@ int gr_bn_running_update(float* running_mean, float* running_var, int64_t* num_b
  * their gradient is zero, so y [y_rows][c] can be exactly the next layer's input and no zero-padded gradient is
  * ever built.  c in {4, 8, 16, 32, 64}, na + nb <= 1024; `part`: a workspace of
  * gr_stem1_scratch_doubles(nimg, na + nb, c) doubles; stats as gr_bn_act_forward.
+ * Every stem entry point takes the image side as a gr_stem_image and the BatchNorm + activation as a gr_bn_act
+ * (ABI 9; gr_stem.hip), then what is specific to the call.
  */
+typedef struct gr_stem_image {
+  const float* obs;    /* image b at obs + (rows ? rows[b] : b) * ld + off */
+  int64_t ld, off;
+  const int64_t* rows; /* the batch's row indices into obs, or NULL */
+  int32_t nimg;
+  const int16_t* pix;  /* [(na + nb) * 9] pixel offsets: table a's cells, then table b's */
+  int32_t na, nb;
+  const float* conv_w; /* [c][9] */
+  int32_t c;
+} gr_stem_image;
+/* A BatchNorm (batch statistics) and the activation after it.  w / b: the affine pair [c] (16-byte aligned).
+ * stats [4][c] (16-byte aligned): WRITTEN by the forwards (gr_stem1_forward, gr_stem12_forward), READ by the
+ * backwards and by the *_bnact GEMMs.  eps: read by the forwards only.  act: GR_POLICY_ACT_LRELU (negative slope
+ * `slope`) or GR_POLICY_ACT_ELU (alpha 1). */
+typedef struct gr_bn_act {
+  const float* w;
+  const float* b;
+  float* stats;
+  int32_t c;
+  float eps;
+  int32_t act;
+  float slope;
+} gr_bn_act;
 int64_t gr_stem1_scratch_doubles(int32_t nimg, int32_t rows_per_img, int32_t c);
-int gr_stem1_forward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                     int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b, float eps,
-                     int32_t act, float slope, float* y, int64_t y_rows, float* stats, double* part, void* stream);
-int gr_stem1_backward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                      int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                      const float* stats, int32_t act, float slope, const float* gy, int64_t gy_rows, float* g_conv_w,
+int gr_stem1_forward(const gr_stem_image* img, const gr_bn_act* bn, float* y, int64_t y_rows, double* part,
+                     void* stream);
+int gr_stem1_backward(const gr_stem_image* img, const gr_bn_act* bn, const float* gy, int64_t gy_rows, float* g_conv_w,
                       float* g_bn_w, float* g_bn_b, double* part, void* stream);
 /* Tall-skinny patch GEMM: C[m][n] = A[m][k] B[k][n] (fp32; A rows `lda` floats apart, 4-byte aligned; C rows `ldc`
  * apart), B small and held in registers: with b_nk B = b^T for b [n][k] (a Conv2d / Linear forward, x W^T), else B = b
@@ -484,18 +497,16 @@ int gr_stem1_backward(const float* obs, int64_t ld, int64_t off, const int64_t* 
 int gr_tsgemm(const float* a, int64_t lda, const float* b, int32_t b_nk, float* c, int64_t ldc, int64_t m, int32_t k,
               int32_t n, void* stream);
 /* The same GEMMs with a BatchNorm + activation applied to A as it is loaded: A = act(bn(z)) with the batch statistics
- * `stats` [4][bn_c] (gr_bn_stats / gr_bn_act_forward's), affine bn_w / bn_b, act GR_POLICY_ACT_LRELU (slope) or ELU;
- * column k of z is channel k % bn_c (bn_c 32 for gr_tsgemm_bnact).  The vision stem's block 2 feeds conv3 this way (vision_actor_critic.py:93-105:
+ * bn->stats [4][bn->c] (gr_bn_stats / gr_bn_act_forward's), its affine pair and activation (bn->eps is not read);
+ * column k of z is channel k % bn->c (bn->c 32 for gr_tsgemm_bnact).  The vision stem's block 2 feeds conv3 this way (vision_actor_critic.py:93-105:
  * BatchNorm2d(32) -> LeakyReLU -> Conv2d(32, 64, 2, 2)): act(bn(z2)) is never written.  gr_tsgemm_bnact: conv3's
  * forward (k 128, n 64, b = W3 [64][128]); gr_patch_wgrad_bnact: its weight gradient gy^T act(bn(z)) (n a multiple
- * of 64, bn_c a multiple of 8 dividing 128).  Values bit-identical to the materialised act(bn(z)) (gr_bn_act_forward's
+ * of 64, bn->c a multiple of 8 dividing 128).  Values bit-identical to the materialised act(bn(z)) (gr_bn_act_forward's
  * arithmetic). */
 int gr_tsgemm_bnact(const float* z, int64_t lda, const float* b, float* c, int64_t ldc, int64_t m, int32_t k, int32_t n,
-                    int32_t bn_c, const float* stats, const float* bn_w, const float* bn_b, int32_t act, float slope,
-                    void* stream);
+                    const gr_bn_act* bn, void* stream);
 int gr_patch_wgrad_bnact(const float* z, int64_t ld, const float* gy, int64_t m, int32_t n, int32_t k, float* part,
-                         float* gw, int32_t bn_c, const float* stats, const float* bn_w, const float* bn_b, int32_t act,
-                         float slope, void* stream);
+                         float* gw, const gr_bn_act* bn, void* stream);
 /* A training-mode BatchNorm's batch statistics alone (gr_bn_act_forward's stats pass): stats [4][c] = mean, invstd,
  * biased var, unbiased var of x [m][c]; `part` as gr_bn_act_forward's. */
 int gr_bn_stats(const float* x, int64_t m, int32_t c, float eps, float* stats, double* part, void* stream);
@@ -515,9 +526,7 @@ int gr_patch_wgrad(const float* x, int64_t ld, const float* gy, int64_t m, int32
  * Same workspace and stats as gr_stem1_forward.  y may be NULL (a forward with no backward: y is only kept for
  * conv2's weight gradient).  moments (64 doubles, 8-byte aligned, may be NULL): the statistics pass's pixel moments
  * over every cell (sums of d = p - p0 and of d d^T, and p0), for gr_stem12_backward_w2. */
-int gr_stem12_forward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                      int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b, float eps,
-                      int32_t act, float slope, const float* w2f, int32_t n2, float* y, float* z2, float* stats,
+int gr_stem12_forward(const gr_stem_image* img, const gr_bn_act* bn, const float* w2f, int32_t n2, float* y, float* z2,
                       double* moments, double* part, void* stream);
 /* The same backward when the next layer is the stem's conv2, Conv2d(c = 16, 32, 3, stride 3, no bias), on the
  * nimg x na table-a rows grouped as its patches (row 9 p + j of an image = position j of patch p, na = 9 n2): takes
@@ -525,9 +534,7 @@ int gr_stem12_forward(const float* obs, int64_t ld, int64_t off, const int64_t* 
  * instead of reading a [nimg * na][16] gy (VisionActorCritic stem; reference vision_actor_critic.py:93-105).
  * w2t: conv2's weight as [9][4][16][8] floats, w2t[((j * 4 + g) * 16 + ch) * 8 + s] = W[o = 8 g + s][ch][j / 3][j % 3]
  * (16-byte aligned).  conv2's own weight gradient is not computed here.  Same workspace as gr_stem1_backward. */
-int gr_stem12_backward(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix, int32_t na,
-                       int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                       const float* stats, int32_t act, float slope, const float* gz2, int32_t n2, const float* w2t,
+int gr_stem12_backward(const gr_stem_image* img, const gr_bn_act* bn, const float* gz2, int32_t n2, const float* w2t,
                        float* g_conv_w, float* g_bn_w, float* g_bn_b, double* part, void* stream);
 /* gr_stem12_backward plus conv2's own weight gradient g_w2 [32][144] (columns (j, ch), w2's layout in
  * VisionActorCritic's patch GEMM): y1 = act(bn(conv1)) is recomputed from the image (bit-identical to the forward's),
@@ -537,9 +544,7 @@ int gr_stem12_backward(const float* obs, int64_t ld, int64_t off, const int64_t*
  * moments: the same forward's (gr_stem12_forward), or NULL: with them the conv1 weight gradient's sums of the pixels
  * and of xhat x pixels come from the moments in fp64 and the pass skips those products. */
 int64_t gr_stem12_backward_w2_scratch_doubles(int32_t nimg);
-int gr_stem12_backward_w2(const float* obs, int64_t ld, int64_t off, const int64_t* rows, int32_t nimg, const int16_t* pix,
-                          int32_t na, int32_t nb, const float* conv_w, int32_t c, const float* bn_w, const float* bn_b,
-                          const float* stats, const double* moments, int32_t act, float slope, const float* gz2,
+int gr_stem12_backward_w2(const gr_stem_image* img, const gr_bn_act* bn, const double* moments, const float* gz2,
                           int32_t n2, const float* w2t, float* g_conv_w, float* g_bn_w, float* g_bn_b, float* g_w2,
                           double* part, void* stream);
 

@@ -13,22 +13,20 @@ Stamps of the step kernel (lane 0 of each wave, s_memtime shader cycles; 9/10 s_
 """
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "variants", "stamps")  # (not under build/: .gpurunignore keeps build/ off the box)
-CSRC = os.path.join(ROOT, "generalizableracing_amd", "csrc")
 PHASES = ["obs_noise", "table_barrier", "ctrl_integrate", "collision", "reward_term", "reset_advance",
           "obs_store_issue", "log"]
 
 
 def build():
-    os.makedirs(OUT, exist_ok=True)
-    cmd = (f"/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off "
-           f"-fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize -DGR_STAMPS -shared -o {OUT}/libgr.so "
-           f"{CSRC}/gr_kernels.hip {CSRC}/gr_camera.hip {CSRC}/gr_policy.hip {CSRC}/gr_policy_f32.hip {CSRC}/gr_bn.hip {CSRC}/gr_update.hip -x hip {CSRC}/gr_capi.cpp")
-    subprocess.run(cmd, shell=True, check=True)
+    """variants/stamps/libgr.so: the tree's sources with -DGR_STAMPS, through csrc/Makefile (scripts/build_patched.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import build_patched
+
+    build_patched.build("stamps", [], "-DGR_STAMPS")
 
 
 ROLE_PHASES = {

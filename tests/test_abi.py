@@ -135,6 +135,12 @@ def test_mlp_rejects_rows_past_32_bit_offsets():
     assert lib.gr_mlp_forward(C.byref(a), None) == -1
 
 
+def _stem_structs(p, c=16, na=720, nb=48, act=_abi.GR_POLICY_ACT_LRELU, bn_c=None):
+    """(gr_stem_image, gr_bn_act) of 8 images of 72 x 96 (row stride 6928, offset 16) on the dummy pointer p."""
+    image = _abi.GrStemImage(p, 6928, 16, None, 8, p, na, nb, p, c)
+    return image, _abi.GrBnAct(p, p, p, c if bn_c is None else bn_c, 1e-5, act, 0.01)
+
+
 def test_stem12_rejects_shapes_it_does_not_cover():
     """gr_stem12_backward (the first block's backward with conv2's input gradient inside) covers 16 channels and table-a
     rows grouped as conv2's patches (na = 9 n2) with 16-byte aligned gz2 / w2t: anything else is an argument error,
@@ -142,11 +148,12 @@ def test_stem12_rejects_shapes_it_does_not_cover():
     lib = _abi.load()
     p = 0x10000  # aligned dummy device pointers: the checks return before any launch
 
-    def call(c=16, na=720, nb=48, n2=80, gz2=p, w2t=p, act=_abi.GR_POLICY_ACT_LRELU):
-        return lib.gr_stem12_backward(p, 6928, 16, None, 8, p, na, nb, p, c, p, p, p, act, 0.01, gz2, n2, w2t, p, p, p, p,
-                                      None)
+    def call(c=16, na=720, nb=48, n2=80, gz2=p, w2t=p, act=_abi.GR_POLICY_ACT_LRELU, bn_c=None):
+        image, bn = _stem_structs(p, c, na, nb, act, bn_c)
+        return lib.gr_stem12_backward(C.byref(image), C.byref(bn), gz2, n2, w2t, p, p, p, p, None)
 
     assert call(c=8) == -1
+    assert call(bn_c=32) == -1         # the BatchNorm's channels are the conv's
     assert call(na=721) == -1          # na != 9 n2
     assert call(n2=0, na=0) == -1
     assert call(gz2=p + 4) == -1       # gz2 not 16-byte aligned
@@ -162,8 +169,8 @@ def test_stem12_w2_backward_rejects_shapes_it_does_not_cover():
     p = 0x10000
 
     def call(c=16, na=720, nb=48, n2=80, gz2=p, w2t=p, gw2=p, act=_abi.GR_POLICY_ACT_LRELU, mom=None):
-        return lib.gr_stem12_backward_w2(p, 6928, 16, None, 8, p, na, nb, p, c, p, p, p, mom, act, 0.01, gz2, n2, w2t,
-                                         p, p, p, gw2, p, None)
+        image, bn = _stem_structs(p, c, na, nb, act)
+        return lib.gr_stem12_backward_w2(C.byref(image), C.byref(bn), mom, gz2, n2, w2t, p, p, p, gw2, p, None)
 
     assert call(c=8) == -1
     assert call(n2=81, na=729) == -1   # past the 80 patches the kernel holds
@@ -184,8 +191,8 @@ def test_stem12_forward_rejects_shapes_it_does_not_cover():
     p = 0x10000
 
     def call(c=16, na=720, n2=80, w2f=p, z2=p, act=_abi.GR_POLICY_ACT_LRELU, mom=None):
-        return lib.gr_stem12_forward(p, 6928, 16, None, 8, p, na, 48, p, c, p, p, 1e-5, act, 0.01, w2f, n2, p, z2, p, mom,
-                                     p, None)
+        image, bn = _stem_structs(p, c, na, 48, act)
+        return lib.gr_stem12_forward(C.byref(image), C.byref(bn), w2f, n2, p, z2, mom, p, None)
 
     assert call(c=32) == -1
     assert call(na=718) == -1
@@ -218,6 +225,19 @@ def test_patch_wgrad_rejects_shapes_it_does_not_cover():
     assert call(x=p + 2) == -1
     assert call(gy=p + 4) == -1
     assert call(gy=None) == -1
+
+    # ... with a BatchNorm + activation on x as it is loaded (gr_patch_wgrad_bnact): n a multiple of 64, the
+    # BatchNorm's channels a multiple of 8 dividing 128, its buffers and activation as gr_bn_act_forward's
+    def call_bn(n=64, k=128, bn_c=32, act=_abi.GR_POLICY_ACT_LRELU, stats=p, bn=True):
+        b = _abi.GrBnAct(p, p, stats, bn_c, 0.0, act, 0.01)
+        return lib.gr_patch_wgrad_bnact(p, k, p, 100, n, k, p, p, C.byref(b) if bn else None, None)
+
+    assert call_bn(n=32, k=144) == -1
+    assert call_bn(bn_c=4) == -1
+    assert call_bn(bn_c=64 + 32) == -1
+    assert call_bn(act=3) == -1
+    assert call_bn(stats=None) == -1
+    assert call_bn(bn=False) == -1
 
 
 def test_bn_running_update_rejects_bad_arguments():
@@ -254,6 +274,17 @@ def test_tsgemm_rejects_shapes_it_does_not_cover():
     assert call(a=p + 2) == -1
     assert call(a=None) == -1
 
+    # ... with a BatchNorm + activation on A as it is loaded (gr_tsgemm_bnact): conv3's forward alone, 32 channels
+    def call_bn(k=128, n=64, bn_c=32, act=_abi.GR_POLICY_ACT_LRELU, w=p, bn=True):
+        b = _abi.GrBnAct(w, p, p, bn_c, 0.0, act, 0.01)
+        return lib.gr_tsgemm_bnact(p, k, p, p, n, 100, k, n, C.byref(b) if bn else None, None)
+
+    assert call_bn(k=64, n=128) == -1
+    assert call_bn(bn_c=16) == -1
+    assert call_bn(act=2) == -1
+    assert call_bn(w=None) == -1
+    assert call_bn(bn=False) == -1
+
 
 def test_l2c2_mix_rows_rejects_bad_arguments():
     """gr_l2c2_mix_rows: both row-index arrays, cols a multiple of 4, ld >= cols and a multiple of 4, 16-byte aligned
@@ -280,7 +311,7 @@ def _header_source():
 
 
 def test_struct_layouts_match_header(tmp_path):
-    """sizeof and every field's offsetof of the 13 argument structs, from a C program compiled against include/gr.h,
+    """sizeof and every field's offsetof of the 15 argument structs, from a C program compiled against include/gr.h,
     equal the ctypes mirrors' (a mirror field the header does not have fails the compile)."""
     cc = shutil.which("cc")
     if cc is None:
@@ -292,7 +323,7 @@ def test_struct_layouts_match_header(tmp_path):
         for field, _ in mirror._fields_:
             lines.append(f'printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));')
             expected[f"{cname}.{field}"] = getattr(mirror, field).offset
-    assert len(_abi.STRUCTS) == 13
+    assert len(_abi.STRUCTS) == 15
     prog = tmp_path / "layout.c"
     prog.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "gr.h"\nint main(void) {\n  '
                     + "\n  ".join(lines) + "\n  return 0;\n}\n")
