@@ -713,7 +713,9 @@ int gr_offline_pgd_step(const float* features, const int8_t* supervision, const 
  *   gr_ppo_loss_forward : sums [3] = [sum max(surrogate, clipped), sum value term, sum KL]  (means: / rows)
  *   gr_ppo_loss_backward: g [2] = upstream gradients of the surrogate and value means (device scalars);
  *                         dmu [rows][k], dvalue [rows], dstd [k] (summed over the rows)
- * `partial` is caller-owned scratch of gr_ppo_loss_partials(rows) floats. */
+ * `partial` is caller-owned scratch of gr_ppo_loss_partials(rows) floats.
+ * Row strides: ld_mu, ld_act, ld_mu_old and ld_sig_old >= k, the scalar columns' (ld_value, ld_logp_old, ld_adv,
+ * ld_value_old, ld_ret) >= 1, else GR_ERR_ARG: a broadcast sig_old with row stride 0 is rejected (materialise it). */
 typedef struct {
   int64_t rows;
   int32_t k;
