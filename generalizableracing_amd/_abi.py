@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 9
+GR_ABI_VERSION = 10
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -212,8 +212,7 @@ class GrPolicyArgs(C.Structure):
 
 class GrMlpNet(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "w3", "b3", "h1", "z2", "y", "gy", "gz2",
-                                          "grads")] + [("ldx", C.c_int64), ("d", C.c_int32), ("k", C.c_int32),
-                                                       ("h1mask", C.c_void_p)]
+                                          "grads")] + [("ldx", C.c_int64), ("d", C.c_int32), ("k", C.c_int32)]
 
 
 class GrMlpArgs(C.Structure):
@@ -302,7 +301,6 @@ SIGNATURES = {
     "gr_terrain_stage": (C.c_int, [vp, vp, vp, C.POINTER(GrObstacles), vp]),
     "gr_terrain_commit": (C.c_int, [vp, vp]),
     "gr_terrain_epoch": (i64, [vp]),
-    "gr_mlp_h1mask_words": (i64, [i64, i32]),
     "gr_bind_buffers": (C.c_int, [vp, C.POINTER(GrBuffers)]),
     "gr_bind_obs_sink": (C.c_int, [vp, vp, vp, C.c_int]),
     "gr_init": (C.c_int, [vp, vp]),

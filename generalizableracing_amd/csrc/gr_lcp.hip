@@ -16,27 +16,19 @@
 //             (mlp_fwd's chain with x := gb, no biases, a mask multiply where the activation was; the small weight
 //             gradients on MFMA contracting over the tile's rows as in mlp_bwd), one partial row per workgroup.
 //   gW2 = v2^T s1 is mlp_wgrad (gr_mlp.hip) on (gz2 := v2, h1 := s1); lcp_final sums every partial in a fixed order.
-// No atomics; every sum has a fixed order, so the results are bit-reproducible.  MFMA fragment convention: gr_mlp.hip.
+// No atomics; every sum has a fixed order, so the results are bit-reproducible.  The MFMA fragment convention,
+// the fragment helpers, the tile geometry (MW waves, BE-row tiles) and what these passes share with gr_mlp.hip's:
+// gr_mfma.h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/gr.h"
 #include "gr_kernels.h"
+#include "gr_mfma.h"
 
 namespace gr {
 namespace lcp {
 
-typedef float m4 __attribute__((ext_vector_type(4)));
-
-constexpr int MW = 8;          // waves per workgroup
-constexpr int BC = 2;          // 16-row column tiles per workgroup tile
-constexpr int BE = 16 * BC;    // rows per workgroup tile
 constexpr int L_BLOCKS = 256;  // persistent workgroups (one per CU)
-
-__device__ __forceinline__ m4 mf(float a, float b, m4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ m4 ld4(const float* p) { return *reinterpret_cast<const m4*>(p); }
-__device__ __forceinline__ void st4(float* p, m4 v) { *reinterpret_cast<m4*>(p) = v; }
-__device__ __forceinline__ float lrelu_d(float z, float s) { return z > 0.0f ? 1.0f : s; }
-__device__ __forceinline__ m4 zero4() { return (m4){0.0f, 0.0f, 0.0f, 0.0f}; }
 
 struct Args {
   const float* mu;   // [rows][ld_mu], first k columns
@@ -98,19 +90,13 @@ __global__ __launch_bounds__(MW * 64) void lcp_fwd(Args a) {
   const float* __restrict__ W2 = a.w2;
   const float* __restrict__ W3 = a.w3;
 
-  // A operands (as mlp_bwd): row j of tile t is hidden unit i = 16 (wave TW + t) + j of h1, k step 4 q + r is z2
-  // unit 16 q + 4 g + r: W2[16 q + 4 g + r][i]; W3^T: row j = unit, k = output g
+  // A operands (as mlp_bwd): row j of tile t is hidden unit 16 (wave TW + t) + j of h1
   float w2c[TW][4 * Q], w3a[TW];
   // g^T = W1^T v1^T over the wave's units: row j = input 16 dt + j, k step r of tile t = unit 16 (wave TW + t) + 4 g + r
   float w1a[TW][DT][4];
 #pragma unroll
   for (int t = 0; t < TW; ++t) {
-    const int i = 16 * (wave * TW + t) + j;
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w2c[t][4 * q + r] = W2[(size_t)(16 * q + 4 * g + r) * H + i];
-    w3a[t] = g < K ? W3[(size_t)g * H + i] : 0.0f;
+    load_w2_column<H>(W2, W3, K, 16 * (wave * TW + t) + j, g, w2c[t], w3a[t]);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -426,21 +412,7 @@ __global__ __launch_bounds__(MW * 64) void lcp_bwd(Args a, int row_floats) {
   // ---- the workgroup's partial row [gW1 | gW3 | dstd]
   float* pr = a.part + (size_t)blockIdx.x * (size_t)row_floats;
 #pragma unroll
-  for (int t = 0; t < TW; ++t) {
-    const int u0 = 16 * (wave * TW + t);
-    // gW1 [H][D]: C rows = units u0 + 4 g + q, col = input 16 dt + j
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (16 * dt + j < D) pr[(size_t)(u0 + 4 * g + q) * D + 16 * dt + j] = gw1[t][dt][q];
-    // gW3 [k][H]: C rows = outputs 4 g + q (g == 0, q < k), col = unit u0 + j
-    if (g == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (q < K) pr[H * D + q * H + u0 + j] = gw3[t][q];
-    }
-  }
+  for (int t = 0; t < TW; ++t) store_gw1_gw3<H, DT>(pr, H * D, 16 * (wave * TW + t), D, K, g, j, gw1[t], gw3[t]);
   // dstd: waves 0 and 1 hold it, output kk = lane & 3 (fixed butterfly over the lanes of one output, then the waves)
   if (wave < 2) {
     float v = dstd;
@@ -475,22 +447,7 @@ __global__ __launch_bounds__(LF_WAVES * 64) void lcp_final(const float* __restri
     rows = splits;
     ldr = H * H;
   }
-  m4 acc0 = zero4(), acc1 = zero4();
-  if (src) {
-    int b = wv;
-    for (; b + 7 * LF_WAVES < rows; b += 8 * LF_WAVES) {  // 8 loads in flight per lane
-      m4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = ld4(src + (size_t)(b + u * LF_WAVES) * ldr);
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        acc0 += v[u];
-        acc1 += v[u + 1];
-      }
-    }
-    for (; b < rows; b += LF_WAVES) acc0 += ld4(src + (size_t)b * ldr);
-  }
-  sm[threadIdx.x] = acc0 + acc1;
+  sm[threadIdx.x] = partial_rows_sum<LF_WAVES>(src, rows, ldr, wv);
   __syncthreads();
   if (wv == 0 && src) {
     m4 t = sm[lane];
@@ -517,35 +474,14 @@ static int grid_x(long long rows) {
   return t < L_BLOCKS ? (t < 1 ? 1 : (int)t) : L_BLOCKS;
 }
 
-template <typename F>
-static hipError_t set_lds(F* k, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 template <int H, int DT>
 static hipError_t launch_fwd_t(const Args& a, hipStream_t s) {
-  static bool attr = false;
-  const size_t lds = fwd_lds_bytes(H, DT);
-  if (!attr) {
-    const hipError_t e = set_lds(&lcp_fwd<H, DT>, lds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((lcp_fwd<H, DT>), dim3(grid_x(a.rows)), dim3(MW * 64), lds, s, a);
-  return hipGetLastError();
+  return launch_lds<lcp_fwd<H, DT>>(dim3(grid_x(a.rows)), dim3(MW * 64), fwd_lds_bytes(H, DT), s, a);
 }
 
 template <int H, int DT>
 static hipError_t launch_bwd_t(const Args& a, int row, hipStream_t s) {
-  static bool attr = false;
-  const size_t lds = bwd_lds_bytes(H);
-  if (!attr) {
-    const hipError_t e = set_lds(&lcp_bwd<H, DT>, lds);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  hipLaunchKernelGGL((lcp_bwd<H, DT>), dim3(grid_x(a.rows)), dim3(MW * 64), lds, s, a, row);
-  return hipGetLastError();
+  return launch_lds<lcp_bwd<H, DT>>(dim3(grid_x(a.rows)), dim3(MW * 64), bwd_lds_bytes(H), s, a, row);
 }
 
 }  // namespace lcp

@@ -351,12 +351,9 @@ class _FusedMLPsFn(torch.autograd.Function):
             for name, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("w3", w3), ("b3", b3)):
                 setattr(s, name, t.data_ptr())
             s.h1, s.z2, s.y = h1.data_ptr(), z2.data_ptr(), y.data_ptr()
-            # the sign of h1 as bits (H = 256: the backward reads these instead of the h1 rows, mlp_bwd256h)
-            mask = torch.empty(_mask_words(rows, h), device=dev, dtype=torch.int64)
-            s.h1mask = mask.data_ptr() if mask.numel() else None
             a.net[i] = s
             a.hidden = h
-            keep += [h1, z2, mask]
+            keep += [h1, z2]
             outs.append(y)
         _abi.call("gr_mlp_forward", C.byref(a), _abi.raw_stream(xs[0].device))
         ctx.nnets, ctx.slope = nnets, float(slope)
@@ -370,7 +367,7 @@ class _FusedMLPsFn(torch.autograd.Function):
     def backward(ctx, *gys):
         nnets = ctx.nnets
         saved = ctx.saved_tensors
-        xs, keep, params = saved[:nnets], saved[nnets:4 * nnets], saved[4 * nnets:]
+        xs, keep, params = saved[:nnets], saved[nnets:3 * nnets], saved[3 * nnets:]
         rows = xs[0].shape[0]
         dev = xs[0].device
         a = GrMlpArgs()
@@ -379,7 +376,7 @@ class _FusedMLPsFn(torch.autograd.Function):
         for i in range(nnets):
             w1, b1, w2, b2, w3, b3 = params[6 * i:6 * i + 6]
             h, d, k = w1.shape[0], w1.shape[1], w3.shape[0]
-            h1, z2, mask = keep[3 * i], keep[3 * i + 1], keep[3 * i + 2]
+            h1, z2 = keep[2 * i], keep[2 * i + 1]
             gy = gys[i]
             gy = torch.zeros(rows, k, device=dev, dtype=torch.float32) if gy is None else gy.float().contiguous()
             gys_keep.append(gy)
@@ -395,7 +392,6 @@ class _FusedMLPsFn(torch.autograd.Function):
             gz2 = torch.empty_like(z2)
             gys_keep.append(gz2)
             s.h1, s.z2, s.gy, s.gz2, s.grads = h1.data_ptr(), z2.data_ptr(), gy.data_ptr(), gz2.data_ptr(), grads.data_ptr()
-            s.h1mask = mask.data_ptr() if mask.numel() else None
             a.net[i] = s
             a.hidden = h
             o = 0
@@ -411,19 +407,6 @@ class _FusedMLPsFn(torch.autograd.Function):
         a.partial = part.data_ptr()
         _abi.call("gr_mlp_backward", C.byref(a), _abi.raw_stream(xs[0].device))
         return (None, None, None) + (None,) * nnets + tuple(grads_out)
-
-
-# True: the forward also writes the sign of h1 as bits and the backward (H = 256) reads those instead of the h1 rows
-# (mlp_bwd256h, two workgroups per CU).  Measured no faster than mlp_bwd256 (C2 +2 %, 393 216 rows -3 %, the
-# forward's mask +2 %; DESIGN §4f''), so off by default; tests run both.
-_H1_MASKS = False
-
-
-def _mask_words(rows: int, hidden: int) -> int:
-    """gr_mlp_h1mask_words for H = 256 (mlp_bwd256h); 0 (no mask: the backward reads h1) for H = 128."""
-    if hidden != 256 or not _H1_MASKS:
-        return 0
-    return int(_abi.load().gr_mlp_h1mask_words(rows, hidden))
 
 
 def _sink_region(params):

@@ -40,8 +40,9 @@ extern "C" {
  * (`rows` after `off`).  5: gr_stem12_backward_w2 (conv2's weight gradient inside the first block's backward).
  * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward
  * 8: gr_offline_collect / gr_offline_pgd_step.  9: gr_stem_image / gr_bn_act in place of the stem entry points' and the
- * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit) */
-#define GR_ABI_VERSION 9
+ * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit).  10: gr_mlp_net.h1mask
+ * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired) */
+#define GR_ABI_VERSION 10
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -620,12 +621,7 @@ typedef struct gr_mlp_net {
   float* grads;      /* backward output [H d | H | H H | H | k H | k] = gW1, gb1, gW2, gb2, gW3, gb3 */
   int64_t ldx;
   int32_t d, k;
-  /* optional, 16-byte aligned, gr_mlp_h1mask_words(rows, H) words: the sign of h1 as bits, written by the forward
-   * when non-null; given to the backward (H = 256) it replaces the h1 rows there (mlp_bwd256h: 1/32 of their bytes,
-   * two workgroups per CU).  NULL in the backward: the h1 rows are read (mlp_bwd256 / mlp_bwd). */
-  uint64_t* h1mask;
 } gr_mlp_net;
-int64_t gr_mlp_h1mask_words(int64_t rows, int32_t hidden);
 typedef struct gr_mlp_args {
   gr_mlp_net net[2];
   int64_t rows;
