@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 10
+GR_ABI_VERSION = 11
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -362,6 +362,13 @@ SIGNATURES = {
     # (mu, ld, act, ld, std, h1, z2, w1, w2, w3, rows, H, d, k, slope, ...)
     "gr_lcp_forward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 6),
     "gr_lcp_backward": (C.c_int, [vp, i64, vp, i64] + [vp] * 6 + [i64, i32, i32, i32, f32] + [vp] * 10),
+    "gr_gru_scratch_floats": (i64, [i64, i64, i32]),
+    # (x, ldx, h, h_prev_out, w_ih, w_hh, b_ih, b_hh, n, d, R, stream)
+    "gr_gru_step": (C.c_int, [vp, i64, vp, vp] + [vp] * 4 + [i64, i32, i32, vp]),
+    # (x, ldx_t, ldx_b, h0, dones, ld_dones, w_ih, w_hh, b_ih, b_hh, t, b, d, R, out, gates, stream)
+    "gr_gru_seq_forward": (C.c_int, [vp, i64, i64, vp, vp, i64] + [vp] * 4 + [i32, i64, i32, i32, vp, vp, vp]),
+    # (gout, x, ldx_t, ldx_b, h0, dones, ld_dones, w_hh, out, gates, t, b, d, R, scratch, grads, stream)
+    "gr_gru_seq_backward": (C.c_int, [vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
     "gr_offline_scratch_ints": (i64, [i64]),
     # (feat, ld, aux, ld, n, d, features, supervision, capacity, cursor, scratch, stream)
     "gr_offline_collect": (C.c_int, [vp, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp]),

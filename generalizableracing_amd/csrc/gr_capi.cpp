@@ -1229,6 +1229,53 @@ int gr_lcp_backward(const float* mu, int64_t ld_mu, const float* act, int64_t ld
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
+// the sizes the GRU kernels cover (gr_gru.hip) and the 32-bit row limit of their [T B][4R] buffers
+static bool gru_sizes_ok(int64_t t, int64_t b, int32_t d, int32_t r) {
+  if (r != 64 && r != 128 && r != 192 && r != 256) return false;
+  if (d < 1 || d > 64 || t < 1 || t > 64 || b < 1) return false;
+  return b <= (int64_t)GR_MLP_MAX_ELEMS / (t * 4 * r);
+}
+
+int64_t gr_gru_scratch_floats(int64_t t, int64_t b, int32_t r) {
+  if (!gru_sizes_ok(t, b, 1, r)) return GR_ERR_ARG;
+  return gr::gru_scratch_floats(t, b, r);
+}
+
+int gr_gru_step(const float* x, int64_t ldx, float* h, float* h_prev_out, const float* w_ih, const float* w_hh,
+                const float* b_ih, const float* b_hh, int64_t n, int32_t d, int32_t r, void* stream) {
+  if (!gru_sizes_ok(1, n, d, r) || ldx < d || !x || !h || !w_ih || !w_hh || !b_ih || !b_hh || h_prev_out == h ||
+      !aligned16(h) || !aligned16(h_prev_out) || !aligned16(w_hh) || !aligned16(b_ih) || !aligned16(b_hh))
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_forward(x, 0, ldx, h, nullptr, 0, w_ih, w_hh, b_ih, b_hh, 1, n, d, r, h,
+                                              nullptr, h_prev_out, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+int gr_gru_seq_forward(const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0, const uint8_t* dones,
+                       int64_t ld_dones, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       int32_t t, int64_t b, int32_t d, int32_t r, float* out, float* gates, void* stream) {
+  if (!gru_sizes_ok(t, b, d, r) || ldx_b < d || ldx_t < 0 || ld_dones < 0 || !x || !h0 || !dones || !w_ih || !w_hh ||
+      !b_ih || !b_hh || !out || out == h0 || !aligned16(h0) || !aligned16(w_hh) || !aligned16(b_ih) ||
+      !aligned16(b_hh) || !aligned16(out) || !aligned16(gates))
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_forward(x, ldx_t, ldx_b, h0, dones, ld_dones, w_ih, w_hh, b_ih, b_hh, t, b, d, r,
+                                              out, gates, nullptr, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+int gr_gru_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0,
+                        const uint8_t* dones, int64_t ld_dones, const float* w_hh, const float* out,
+                        const float* gates, int32_t t, int64_t b, int32_t d, int32_t r, float* scratch, float* grads,
+                        void* stream) {
+  if (!gru_sizes_ok(t, b, d, r) || ldx_b < d || ldx_t < 0 || ld_dones < 0 || !gout || !x || !h0 || !dones || !w_hh ||
+      !out || !gates || !scratch || !grads || !aligned16(gout) || !aligned16(h0) || !aligned16(out) ||
+      !aligned16(gates) || !aligned16(scratch) || !aligned16(grads))
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_backward(gout, x, ldx_t, ldx_b, h0, dones, ld_dones, w_hh, out, gates, t, b, d,
+                                               r, scratch, grads, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
 int gr_adam_prepare(gr_adam_segment* t, int32_t nseg, int32_t* nblocks) {
   if (!t || !nblocks || nseg < 1 || nseg > GR_ADAM_MAX_SEGMENTS) return GR_ERR_ARG;
   int64_t nb = 0;

@@ -219,6 +219,16 @@ hipError_t launch_lcp_backward(const float* mu, long long ld_mu, const float* ac
                                long long rows, int hidden, int d, int k, float slope, const float* g, const float* v1,
                                const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
                                float* grads, hipStream_t s);
+// gr_gru.hip: the GRU memory's masked sequence (T = 1: the rollout step), its BPTT and the backward's scratch
+int64_t gru_scratch_floats(long long t, long long b, int r);
+hipError_t launch_gru_forward(const float* x, long long ldx_t, long long ldx_b, const float* h0,
+                              const unsigned char* dones, long long ld_dones, const float* w_ih, const float* w_hh,
+                              const float* b_ih, const float* b_hh, int t, long long b, int d, int r, float* out,
+                              float* gates, float* h_prev_out, hipStream_t s);
+hipError_t launch_gru_backward(const float* gout, const float* x, long long ldx_t, long long ldx_b, const float* h0,
+                               const unsigned char* dones, long long ld_dones, const float* w_hh, const float* out,
+                               const float* gates, int t, long long b, int d, int r, float* scratch, float* grads,
+                               hipStream_t s);
 hipError_t launch_in_backward(const float* gh, const float* hv, const float* x, long long m, int d, int ldx, int h,
                               float slope, float* part, float* sums, hipStream_t s);
 // Camera launch (camera_kernel, gr_camera.hip).  Dynamic LDS: the normal table and the ray tables (workgroup), then

@@ -61,7 +61,8 @@ register("DiffLab-Quadcopter-CTBR-Racing-Vision-v0", **_VISION)
 # the state-only task: the same env without the camera (16-dim policy / critic observations) and rsl_rl PPO over
 # MLP(256, 256) (QuadcopterPPORunnerCfg, rsl_rl_ppo_cfg.py:15-41 with BASELINE.json's hidden sizes); the BASELINE
 # configs C2-C5, bench.py and smoke() measure this one.  The L2C2 recipe over the same MLP is a second agent key, the
-# LCP recipe (PPOLCP, the gradient penalty rsl_rl_ppo_cfg.py:102 leaves commented out) a third.
+# LCP recipe (PPOLCP, the gradient penalty rsl_rl_ppo_cfg.py:102 leaves commented out) a third, PPO over the
+# recurrent policy (ActorCriticRecurrent, the GRU of rsl_rl_ppo_cfg.py:64-76) a fourth.
 register(
     "DiffLab-Quadcopter-CTBR-Racing-State-v0",
     entry_point="generalizableracing_amd.envs.racing_env:RacingEnv",
@@ -69,4 +70,5 @@ register(
     rsl_rl_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterPPORunnerCfg",
     rsl_rl_l2c2_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterL2C2PPORunnerCfg",
     rsl_rl_lcp_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterLCPPPORunnerCfg",
+    rsl_rl_recurrent_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterRecurrentPPORunnerCfg",
 )

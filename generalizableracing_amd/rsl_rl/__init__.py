@@ -10,3 +10,5 @@ from .ppo_lcp import PPOLCP  # noqa: F401
 from .config import QuadcopterLCPPPORunnerCfg, RslRlPpoLcpAlgorithmCfg  # noqa: F401
 from .rollout_storage_l2c2 import RolloutStorageL2C2  # noqa: F401
 from .vision_actor_critic import VisionActorCritic  # noqa: F401
+from .actor_critic_recurrent import ActorCriticRecurrent, Memory  # noqa: F401
+from .config import QuadcopterRecurrentPPORunnerCfg, RslRlPpoActorCriticRecurrentCfg  # noqa: F401

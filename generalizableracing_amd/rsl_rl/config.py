@@ -137,3 +137,27 @@ class QuadcopterVisionPPORunnerCfg(QuadcopterPPORunnerCfg):
     policy: RslRlPpoActorCriticCfg = field(default_factory=RslRlPpoVisionActorCriticCfg)
     algorithm: RslRlPpoAlgorithmCfg = field(
         default_factory=lambda: RslRlPpoAlgorithmCfg(class_name="PPOL2C2", entropy_coef=0.005))
+
+
+@dataclass
+class RslRlPpoActorCriticRecurrentCfg(RslRlPpoActorCriticCfg):
+    """The recurrent policy as the reference configures it (rsl_rl_ppo_cfg.py:64-76: GRU, hidden size 192, one layer,
+    heads [128, 128], lrelu), over the state observations."""
+
+    class_name: str = "ActorCriticRecurrent"
+    rnn_type: str = "gru"
+    rnn_hidden_size: int = 192
+    rnn_num_layers: int = 1
+    actor_hidden_dims: list = field(default_factory=lambda: [128, 128])
+    critic_hidden_dims: list = field(default_factory=lambda: [128, 128])
+    # not in the reference: the memories through gr_gru_step / gr_gru_seq_* (rsl_rl/fused_gru.py); False keeps
+    # torch.nn.GRU stepped in a loop
+    fused_gru: bool = True
+
+
+@dataclass
+class QuadcopterRecurrentPPORunnerCfg(QuadcopterPPORunnerCfg):
+    """QuadcopterPPORunnerCfg's algorithm block over ActorCriticRecurrent (a GRU memory before actor and critic)."""
+
+    experiment_name: str = "racing_ppo_recurrent"
+    policy: RslRlPpoActorCriticCfg = field(default_factory=RslRlPpoActorCriticRecurrentCfg)

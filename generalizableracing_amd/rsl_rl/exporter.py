@@ -2,6 +2,8 @@
 Isaac Lab's export_policy_as_jit / export_policy_as_onnx used by standalone/rsl_rl/play.py:100-118).
 
 * `export_policy_as_jit`: TorchScript of normalizer + actor MLP, input the 16-dim state obs.
+* `export_recurrent_policy_as_jit`: TorchScript of normalizer + GRU memory + actor for ActorCriticRecurrent,
+  forward(obs [B,16], h_in [1,B,R]) -> (actions, h_out); the caller carries h and zeroes finished envs' rows.
 * `export_vision_policy_as_jit`: TorchScript of the vision policy with the reference exporter's
   two-input signature forward(state [B,16], depth_image [B,1,72,96]) -> actions
   (+ sigmoid(aux) when the auxiliary head is exported).
@@ -27,6 +29,21 @@ class _PolicyExporter(nn.Module):
 
     def forward(self, x):
         return self.actor(self.normalizer(x))
+
+
+class _RecurrentPolicyExporter(nn.Module):
+    """exporter.py's recurrent branch for the state policy, with the hidden state an explicit input and output
+    (a copy of memory_a.rnn and the actor)."""
+
+    def __init__(self, policy, normalizer=None):
+        super().__init__()
+        self.rnn = copy.deepcopy(policy.memory_a.rnn).cpu()
+        self.actor = copy.deepcopy(policy.actor).cpu()
+        self.normalizer = copy.deepcopy(normalizer).cpu() if normalizer is not None else nn.Identity()
+
+    def forward(self, obs: torch.Tensor, h_in: torch.Tensor):
+        out, h_out = self.rnn(self.normalizer(obs).unsqueeze(0), h_in)
+        return self.actor(out.squeeze(0)), h_out
 
 
 class _VisionPolicyExporter(nn.Module):
@@ -73,8 +90,18 @@ def _normalizer(n):
 
 
 def export_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.pt") -> str:
+    if getattr(policy, "is_recurrent", False):
+        return export_recurrent_policy_as_jit(policy, normalizer, path, filename)
     os.makedirs(path, exist_ok=True)
     m = _PolicyExporter(policy, _normalizer(normalizer)).eval()
+    out = os.path.join(path, filename)
+    torch.jit.script(m).save(out)
+    return out
+
+
+def export_recurrent_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.pt") -> str:
+    os.makedirs(path, exist_ok=True)
+    m = _RecurrentPolicyExporter(policy, _normalizer(normalizer)).eval()
     out = os.path.join(path, filename)
     torch.jit.script(m).save(out)
     return out
@@ -102,6 +129,8 @@ def _onnx_export(module, args, out, input_names, output_names, verbose):
 
 
 def export_policy_as_onnx(policy, path: str, normalizer=None, filename: str = "policy.onnx", verbose=False) -> str:
+    if getattr(policy, "is_recurrent", False):
+        raise RuntimeError("ONNX export of the recurrent policy is not built; use export_recurrent_policy_as_jit")
     os.makedirs(path, exist_ok=True)
     m = _PolicyExporter(policy, _normalizer(normalizer)).eval()
     x = torch.zeros(1, m.actor[0].in_features)

@@ -19,6 +19,7 @@ import torch
 
 from . import distributed as gdist
 from .actor_critic import ActorCritic, EmpiricalNormalization
+from .actor_critic_recurrent import ActorCriticRecurrent
 from .ppo import PPO
 from .ppo_l2c2 import PPOL2C2
 from .ppo_lcp import PPOLCP
@@ -26,7 +27,8 @@ from .rollout_ops import EpisodeStats
 from .vision_actor_critic import VisionActorCritic
 
 ALGORITHMS = {"PPO": PPO, "PPOL2C2": PPOL2C2, "PPOLCP": PPOLCP}
-POLICIES = {"ActorCritic": ActorCritic, "VisionActorCritic": VisionActorCritic}
+POLICIES = {"ActorCritic": ActorCritic, "VisionActorCritic": VisionActorCritic,
+            "ActorCriticRecurrent": ActorCriticRecurrent}
 
 
 class _CsvWriter:

@@ -92,6 +92,23 @@ class PPO:
         self.fused_losses = bool(fused_losses)
         # with the fused losses: the actor and critic MLPs as whole-network fp32-MFMA kernels (linear.fused_mlps)
         self.fused_mlp = bool(fused_mlp)
+        # a policy with memories (ActorCriticRecurrent): the update runs them over each mini-batch's [T, B] block
+        self.recurrent = bool(getattr(policy, "is_recurrent", False))
+        self._refuse_recurrent()
+
+    # what a recurrent policy (ActorCriticRecurrent) cannot be combined with yet, by constructor argument
+    _RECURRENT_REFUSALS = ("graph_update", "fused_rollout_inference", "update_autocast_bf16")
+
+    def _refuse_recurrent(self):
+        if not self.recurrent:
+            return
+        if type(self) is not PPO:
+            raise ValueError(f"{type(self).__name__} does not support a recurrent policy: its extra loss term reads "
+                             "single observations, not sequences; use PPO.")
+        for name in self._RECURRENT_REFUSALS:
+            if getattr(self, name):
+                raise ValueError(f"PPO: {name}=True is not supported with a recurrent policy (the recurrent update "
+                                 "runs eagerly in fp32 and the rollout steps the policy's own memories).")
 
     def flat_grads(self) -> gdist.FlatGrads:
         """The flat gradient buffer over the parameters the loss reaches (all of them until the first mini-batch
@@ -133,6 +150,12 @@ class PPO:
             self.transition.observations = obs
             self.transition.privileged_observations = critic_obs
             return a
+        if self.recurrent and self.storage.step == 0:
+            # ppo.py:72-73 saves the hidden states before acting at every step; the masked sequence needs those of
+            # rollout step 0 only.  The transition carries them to the storage; a memory on the fused step writes
+            # the storage's h0 itself (gr_gru_step's second pointer) and hands None
+            self.transition.hidden_states = self.policy.stage_hidden_states(
+                obs, critic_obs, *self.storage.h0_buffers(*self.policy.get_hidden_sizes()))
         self.transition.actions = self.policy.act(obs).detach()
         self.transition.values = self.policy.evaluate(critic_obs).detach()
         self.transition.actions_log_prob = self.policy.get_actions_log_prob(self.transition.actions).detach()
@@ -240,7 +263,10 @@ class PPO:
                 self.fused.refresh()
             return out
         sums = [torch.zeros((), device=self.device) for _ in self.loss_terms]
-        generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        if self.recurrent:  # ppo.py:106-109
+            generator = self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        else:
+            generator = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
         params = list(self.policy.parameters())
         flat = self.flat_grads()
         flat.bind()
@@ -281,25 +307,49 @@ class PPO:
         the update's sums of the terms (a path whose fused op adds to it adds all its terms and returns none), the KL
         mean goes to kl_out [1] too (given on the adaptive schedule only; the return value is not read), and seed is
         the tensor autograd will be seeded with, for a loss that is its root (fused_loss.combined_loss)."""
+        if self.recurrent:  # ppo.py:123-127: the memories over the block, then the same losses per row
+            return self._recurrent_loss(batch)
         if self._use_fused_losses(batch[0]):  # the same losses as one device op each way (fused_loss.py)
             loss, stats = _floss.ppo_loss(self, *batch[:9], acc=acc, kl_out=kl_out, seed=seed)
             return loss, () if acc is not None else (stats[0], stats[1]), stats[2]
         autocast = self.update_autocast_bf16 and str(self.device).startswith("cuda")
         return self._torch_ppo_loss(*batch[:9], kl_out, draw=acc is None, autocast=autocast)[:3]
 
+    def _recurrent_loss(self, batch):
+        """_minibatch_loss for a recurrent policy: `batch` as recurrent_mini_batch_generator yields it.  The memories
+        run over the [T, B] block (policy.act / evaluate with masks = the block's dones and hidden_states = its h0);
+        from the [T * B]-row memory outputs on, the feed-forward code runs unchanged on the policy's heads."""
+        obs, critic_obs = batch[0], batch[1]
+        (h0_a, h0_c), dones = batch[9], batch[10]
+        pol = self.policy
+        feat_a = pol.memory_a(obs, dones, h0_a)
+        feat_c = pol.memory_c(critic_obs, dones, h0_c)
+        rest = batch[2:9]
+        # (the heads module by module: linear.networks_fusable refuses inputs that need a gradient, as these do)
+        if self._use_fused_losses(feat_a):
+            loss, stats = _floss.ppo_loss(self, feat_a, feat_c, *rest)
+            return loss, (stats[0], stats[1]), stats[2]
+        return self._torch_ppo_loss(feat_a, feat_c, *rest, heads_only=True)[:3]
+
     def _torch_ppo_loss(self, obs, critic_obs, act, val, adv, ret, logp_old, mu_old, sig_old, kl_out=None, draw=True,
-                        autocast=False):
+                        autocast=False, heads_only=False):
         """ppo.py:103-172 as torch ops (CPU, autocast, other policies): _minibatch_loss's triple, then the action
         mean and the value.  draw: through policy.act, whose sample nobody uses but which advances the generator as
         the reference does (the eager loops); torch.normal's check of the std reads back to the host, which a capture
-        forbids, so the graphed steps only set the distribution."""
+        forbids, so the graphed steps only set the distribution.  heads_only: obs / critic_obs are the memories'
+        outputs of a recurrent policy (_recurrent_loss): the actor and the critic heads on them."""
         pol = self.policy
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-            pol.act(obs) if draw else pol.update_distribution(obs)
+            if heads_only:
+                pol.set_distribution(pol.actor(obs), draw)
+            else:
+                pol.act(obs) if draw else pol.update_distribution(obs)
             logp = pol.get_actions_log_prob(act)
-            value = pol.evaluate(critic_obs)
+            value = pol.critic(critic_obs) if heads_only else pol.evaluate(critic_obs)
             mu, sigma, entropy = pol.action_mean, pol.action_std, pol.entropy
-        logp, value, mu, sigma, entropy = (t.float() for t in (logp, value, mu, sigma, entropy))
+        if not heads_only:  # (fp32 from autocast's bf16; the recurrent path has no autocast and keeps a float64
+            # policy, which its CPU golden test steps, in float64)
+            logp, value, mu, sigma, entropy = (t.float() for t in (logp, value, mu, sigma, entropy))
         kl = self._kl_mean(mu, sigma, mu_old, sig_old, kl_out)
         surrogate_loss, value_loss = self._ppo_losses(logp, logp_old, adv, value, val, ret)
         loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()

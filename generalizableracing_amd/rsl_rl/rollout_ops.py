@@ -85,6 +85,7 @@ def store_transition(storage, tr, rewards, dones, time_outs, gamma):
                       ("out_sigma", st.sigma)):
         setattr(a, name, dst[t].data_ptr())
     _abi.call("gr_store_transition", C.byref(a), _abi.raw_stream(rewards.device))
+    st.save_hidden_states(tr.hidden_states)
     st.step += 1
 
 

@@ -57,8 +57,10 @@ class RolloutStorage:
             self.sigma = torch.zeros(T, N, *actions_shape, device=device)
         self.num_transitions_per_env = T
         self.num_envs = N
-        self.saved_hidden_states_a = None
-        self.saved_hidden_states_c = None
+        # recurrent policies: the memories' states at rollout step 0, [N, R] each (h0_buffers; the reference keeps
+        # [T, 1, N, R] per memory, rollout_storage.py:90-108, of which the masked sequence needs step 0 only)
+        self.h0_a = None
+        self.h0_c = None
         self.step = 0
         # observation sink (enable_obs_sink): the env's kernel writes the observations of transition t into
         # slot t itself; slot T holds the rollout's last observations (transition 0 of the next rollout)
@@ -119,7 +121,30 @@ class RolloutStorage:
             self.actions_log_prob[self.step].copy_(transition.actions_log_prob.view(-1, 1))
             self.mu[self.step].copy_(transition.action_mean)
             self.sigma[self.step].copy_(transition.action_sigma)
+        self.save_hidden_states(transition.hidden_states)
         self.step += 1
+
+    def h0_buffers(self, size_a, size_c):
+        """(h0_a [N, size_a], h0_c [N, size_c]), allocated on first use: the memories' states at rollout step 0
+        (save_hidden_states; on the fused path gr_gru_step's second pointer)."""
+        if self.h0_a is None or self.h0_a.shape[1] != size_a or self.h0_c.shape[1] != size_c:
+            # (not inference tensors, though the rollout runs in inference mode: the update's graph holds them)
+            with torch.inference_mode(False):
+                self.h0_a = torch.zeros(self.num_envs, size_a, device=self.device)
+                self.h0_c = torch.zeros(self.num_envs, size_c, device=self.device)
+        return self.h0_a, self.h0_c
+
+    def save_hidden_states(self, hidden_states):
+        """A transition that carries (h_a, h_c) ([1, N, R] or [N, R], taken before acting: ppo.py:72-73) at rollout
+        step 0 sets h0_a / h0_c; later steps' states are not kept.  A None member is a memory whose fused step has
+        written its h0 already (Memory.stage_h0).  Nothing is allocated without hidden states."""
+        if self.step != 0 or hidden_states is None or (hidden_states[0] is None and hidden_states[1] is None):
+            return
+        if self.h0_a is None:
+            self.h0_buffers(*(h.shape[-1] for h in hidden_states))
+        for h0, h in zip((self.h0_a, self.h0_c), hidden_states):
+            if h is not None:
+                h0.copy_(h.reshape(self.num_envs, -1))
 
     def clear(self):
         self.step = 0
@@ -239,3 +264,26 @@ class RolloutStorage:
                 idx = indices[i * mini_batch_size:(i + 1) * mini_batch_size]
                 yield (observations[idx].float(), privileged[idx].float(), actions[idx], values[idx], advantages[idx],
                        returns[idx], old_logp[idx], old_mu[idx], old_sigma[idx], (None, None), None)
+
+    def recurrent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """rollout_storage.py:193-254 in its fixed-shape form: mini-batch i is envs [i N / mb, (i + 1) N / mb) with
+        all T steps, no shuffle.  Yields mini_batch_generator's tuple with the observations as [T, B, D] views, the
+        other fields flattened time-major to [T * B, ...], then (h0_a [1, B, R], h0_c [1, B, R]) and the block's dones
+        [T, B] where the reference yields its saved hidden states and padding masks (the memories mask the carried
+        state with them: ActorCriticRecurrent).  No trajectory split, no padding, no host read-back."""
+        if self.training_type != "rl":
+            raise ValueError("This function is only available for reinforcement learning training.")
+        if self.h0_a is None:
+            raise ValueError("recurrent_mini_batch_generator: no hidden states were stored at rollout step 0")
+        T = self.num_transitions_per_env
+        size = self.num_envs // num_mini_batches
+        priv = self.privileged_observations if self.privileged_observations is not None else self.observations
+        for _ in range(num_epochs):
+            for i in range(num_mini_batches):
+                lo, hi = i * size, (i + 1) * size
+                flat = tuple(x[:, lo:hi].flatten(0, 1) for x in (self.actions, self.values, self.advantages,
+                                                                self.returns, self.actions_log_prob, self.mu,
+                                                                self.sigma))
+                obs = tuple(x[:T, lo:hi].to(self.values.dtype) for x in (self.observations, priv))  # (bf16 storage)
+                h0 = (self.h0_a[lo:hi].unsqueeze(0), self.h0_c[lo:hi].unsqueeze(0))
+                yield obs + flat + (h0, self.dones[:, lo:hi, 0])

@@ -41,8 +41,9 @@ extern "C" {
  * 6: gr_test_camera_slots; gr_stem12_forward / gr_stem12_backward_w2 `moments`.  7: gr_lcp_forward / gr_lcp_backward
  * 8: gr_offline_collect / gr_offline_pgd_step.  9: gr_stem_image / gr_bn_act in place of the stem entry points' and the
  * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit).  10: gr_mlp_net.h1mask
- * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired) */
-#define GR_ABI_VERSION 10
+ * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired).  11: gr_gru_step, gr_gru_seq_forward,
+ * gr_gru_seq_backward, gr_gru_scratch_floats */
+#define GR_ABI_VERSION 11
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -660,6 +661,34 @@ int gr_lcp_backward(const float* mu, int64_t ld_mu, const float* act, int64_t ld
                     int32_t hidden, int32_t d, int32_t k, float slope, const float* g, const float* v1,
                     const float* v2, const float* g_pen, float* s1, float* scratch, float* dmu, float* dstd,
                     float* grads, void* stream);
+
+/* The GRU memory of ActorCriticRecurrent (one layer; torch.nn.GRU's parameters: w_ih [3R][d], w_hh [3R][R], b_ih,
+ * b_hh [3R], gate order r, z, n) on v_mfma_f32_16x16x4_f32, fp32:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h' + b_hr);  z = sigmoid(W_iz x + b_iz + W_hz h' + b_hz);
+ *   n = tanh(W_in x + b_in + r (W_hn h' + b_hn));  h_t = (1 - z) n + z h'
+ *   gr_gru_step        : one rollout step, h [n][R] <- GRU(x [n] rows of ldx floats, h) in place; h_prev_out
+ *                        (nullable) receives the pre-step h.  Zeroing finished envs stays with the caller.
+ *   gr_gru_seq_forward : the masked sequence of a mini-batch in one launch: h' = h0 at t = 0 and
+ *                        out[t-1] (1 - dones[t-1]) after; x element (t, b, k) at x[t ldx_t + b ldx_b + k], dones
+ *                        (t, b) one byte at dones[t ld_dones + b].  Out: out [t][b][R] and, when not null, gates
+ *                        [t][b][4R] = r, z, n, W_hn h' + b_hn for the backward.
+ *   gr_gru_seq_backward: BPTT for gout [t][b][R] = dloss/dout: grads = [gW_ih (3R d) | gW_hh (3R R) | gb_ih (3R) |
+ *                        gb_hh (3R)]; x and h0 are constants (no gradient).  The same step-by-step arithmetic as the
+ *                        rollout step, so gr_gru_step iterated with resets gives gr_gru_seq_forward's bits.
+ * R = 64, 128, 192 or 256; 1 <= d <= 64; 1 <= t <= 64; any b, n >= 1 with t b 4R < GR_MLP_MAX_ELEMS; else
+ * GR_ERR_ARG and nothing is launched.  h, h0, out, gates, gout, w_hh, the biases, scratch and grads 16-byte aligned.
+ * Context-free, on `stream`, graph-capturable, no atomics, fixed summation order (bit-reproducible); `scratch` is
+ * caller-owned, gr_gru_scratch_floats(t, b, R) floats. */
+int64_t gr_gru_scratch_floats(int64_t t, int64_t b, int32_t r);
+int gr_gru_step(const float* x, int64_t ldx, float* h, float* h_prev_out, const float* w_ih, const float* w_hh,
+                const float* b_ih, const float* b_hh, int64_t n, int32_t d, int32_t r, void* stream);
+int gr_gru_seq_forward(const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0, const uint8_t* dones,
+                       int64_t ld_dones, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       int32_t t, int64_t b, int32_t d, int32_t r, float* out, float* gates, void* stream);
+int gr_gru_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0,
+                        const uint8_t* dones, int64_t ld_dones, const float* w_hh, const float* out,
+                        const float* gates, int32_t t, int64_t b, int32_t d, int32_t r, float* scratch, float* grads,
+                        void* stream);
 
 /* The offline auxiliary-head stage (standalone/offline/data_collector.py, standalone/offline/train.py): a balanced
  * (feature, label) dataset kept on the device and the PGD-hardened fine-tune step of a Linear(d, 1) head on it.

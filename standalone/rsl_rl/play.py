@@ -109,6 +109,8 @@ def main(argv=None):
             out = policy(obs)
             actions = out[0] if isinstance(out, tuple) else out
             obs, rew, dones, _ = env.step(actions)
+            if pol_mod.is_recurrent:  # finished envs restart from a zero memory
+                pol_mod.reset(dones)
             ret += rew
             d = dones.bool()
             if bool(d.any()):
