@@ -42,9 +42,12 @@ struct KConst {
 // Constants every wave needs before its first loads / RNG draws: passed by value
 // (one kernarg fetch at entry) instead of through the KConst pointer chain.
 struct KHot {
+  // the first eight words are what the step kernel needs ahead of its first loads and draws (env index, env id, LDS
+  // layout, slice size, RNG key): kept together so that its entry fetches them in one wide scalar load
   int num_envs, num_levels, max_gates, track_stride;
-  int env_id_offset, use_motor_model, obs_noise, lds_tab_vec;  // lds_tab_vec: float4 of LDS table (0: global)
+  int env_id_offset, lds_tab_vec;  // lds_tab_vec: float4 of LDS table (0: global)
   uint32_t seed_lo, seed_hi;
+  int use_motor_model, obs_noise;
   float obs_lin_vel_noise, obs_att_noise;
   float obst_span;  // obstacle grid: cell + 2 margin (m), the side of a hinted grown cell
   int dr_rotor;     // per-env rotor constants (GR_P_ROTOR)

@@ -691,8 +691,23 @@ DEV void reset_draws(const KArgs& a, uint32_t gid, uint32_t ep, float m_ctrl, Re
   sincos_w(r.att[1] * 0.5f, &r.sp, &r.cp);
 }
 
-DEV void reset_apply(const KArgs& a, const Tab& tab, Env& e, const ResetDraws& r) {
-  const gr_config& c = a.kc->cfg;
+// The config scalars of reset_apply under gr_config's names, read together (the curriculum block is seven adjacent
+// words of gr_config).  The gate-only step kernels' episode waves fetch them at entry, under their state loads'
+// latency: read where they are used, each was a scalar load with a full wait of its own on the chain between the two
+// barriers.
+struct ResetCfg {
+  int level_up_threshold, level_down_threshold, noise_curriculum, noise_enhance_threshold, noise_decay_threshold;
+  int num_levels, random_drag;
+  float noise_enhance, noise_decay;
+};
+DEV ResetCfg reset_cfg(const gr_config& c) {
+  return {c.level_up_threshold, c.level_down_threshold, c.noise_curriculum, c.noise_enhance_threshold,
+          c.noise_decay_threshold, c.num_levels, c.random_drag, c.noise_enhance, c.noise_decay};
+}
+
+// C: gr_config (each scalar read where it is used) or ResetCfg (read ahead)
+template <typename C>
+DEV void reset_apply(const C& c, const Tab& tab, Env& e, const ResetDraws& r) {
   int up = e.acc >= c.level_up_threshold, down = e.acc < c.level_down_threshold;
   int lvl = e.lvl + up - down;
   if (lvl >= c.num_levels) lvl = (int)gr_floorf(r.lvl_u * (float)c.num_levels);
@@ -744,7 +759,7 @@ DEV void reset_apply(const KArgs& a, const Tab& tab, Env& e, const ResetDraws& r
 DEV void reset_env(const KArgs& a, const Tab& tab, Env& e, uint32_t gid) {
   ResetDraws r;
   reset_draws(a, gid, (uint32_t)e.epoch + 1u, e.mc, r);
-  reset_apply(a, tab, e, r);
+  reset_apply(a.kc->cfg, tab, e, r);
 }
 
 // ------------------------------------------------------------- observations
@@ -1024,6 +1039,8 @@ __device__ unsigned long long g_stamps[GR_STAMP_WAVES * GR_STAMP_SLOTS];
 #define STAMP(k)
 #define RSTAMP(k)
 #endif
+// stamp of a role's first state loads issued (not returned): a slot no role uses otherwise
+#define GR_STAMP_FIRST_LOAD (role == 2 ? 7 : 6)
 
 // ------------------------------------------------------------- table slice view
 struct Slice {
@@ -1032,11 +1049,11 @@ struct Slice {
   int nvec;           // float4 in the slice
 };
 
+// bt: the workgroup's word of a.blk_types, the terrain types of this workgroup (type = floor(i / (N / T)), IL
+// TerrainImporter layout) derived on the host per workgroup.  The caller reads it (one scalar load) ahead of its
+// state loads, so that its round trip runs beside theirs.
 template <bool USE_LDS>
-DEV Slice block_slice(const KArgs& a, const float4* lds) {
-  // terrain types of this workgroup (type = floor(i / (N / T)), IL TerrainImporter layout),
-  // derived on the host per workgroup: one scalar load
-  const int bt = a.blk_types[blockIdx.x];
+DEV Slice block_slice(const KArgs& a, const float4* lds, int bt) {
   const int t0 = bt & 0xffff, t1 = bt >> 16;
   Slice s;
   s.tab.L = a.h.num_levels;
@@ -1062,9 +1079,10 @@ __global__ __launch_bounds__(GR_BLOCK) void env_kernel(KArgs a, const KConst* __
   const int ii = live ? i : n - 1;  // dead lanes mirror the last env (loads stay in bounds, no stores)
   const uint32_t gid = gid_of(a, ii);
   const uint32_t cnt = a.buf.counters[a.buf.counter_index];
+  const int bt = a.blk_types[blockIdx.x];
   Env e;
   load_env(a, ii, e);
-  const Slice sl = block_slice<USE_LDS>(a, lds_tab);
+  const Slice sl = block_slice<USE_LDS>(a, lds_tab, bt);
   if (USE_LDS) {
     for (int idx = threadIdx.x; idx < sl.nvec; idx += GR_BLOCK) lds_tab[idx] = sl.src[idx];
     __syncthreads();
@@ -1184,18 +1202,37 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
   const bool live = i < n;
   const int ii = live ? i : n - 1;  // dead lanes mirror the last env (loads stay in bounds, no stores)
   const gr_config& c = a.kc->cfg;
+  // Entry order (round 9): one batch of kernarg loads behind one wait, then the read of the workgroup's blk_types
+  // word is issued (a scalar round trip to global memory) and, without waiting for it, each role issues its own state /
+  // istate loads, whose addresses need only kernarg words and the thread id.  slice_loads(), called behind them, waits
+  // for the word and issues the table-slice loads that hang on it: the slice is first needed by commit().  The asm
+  // statement there holds that order: left alone, or behind an empty "+s" pin (whose register copy is an ordinary
+  // instruction), the compiler waits for the word ahead of every role's first load.  (KHot keeps the words of the
+  // entry together, or the env id offset comes in a kernarg fetch and wait of its own in two of the roles.)
   const uint32_t gid = gid_of(a, ii);
+  // The obstacle kernels keep the parent's order (the word waited for and the slice view built ahead of the state
+  // loads, the call counter first, reset_apply's scalars read where they are used): with the new one they measured
+  // 0.05 - 0.13 us slower per launch, more than the parent's own spread.
+  constexpr bool LOADS_FIRST = !OBST;
+  const int bt = a.blk_types[blockIdx.x];
   RSTAMP(9);
   STAMP(0);
-  const Slice sl = block_slice<USE_LDS>(a, lds);
+  Slice sl{};
   // each of the 768 threads stages up to two float4 of the table slice, loaded at entry (clamped
   // loads; extras are not stored): a two-type slice of 8-gate tracks (820 float4) needs no load later
   float4 tr = make_float4(0.0f, 0.0f, 0.0f, 0.0f), tr2 = tr;
-  const bool two = sl.nvec > 3 * GR_BLOCK;
-  if (USE_LDS) {
-    tr = sl.src[min((int)threadIdx.x, sl.nvec - 1)];
-    if (two) tr2 = sl.src[min((int)threadIdx.x + 3 * GR_BLOCK, sl.nvec - 1)];
-  }
+  bool two = false;
+  auto slice_loads = [&]() {
+    STAMP(GR_STAMP_FIRST_LOAD);
+    int b = bt;
+    if constexpr (LOADS_FIRST) __asm__ volatile("s_mov_b32 %0, %1" : "=s"(b) : "s"(__builtin_amdgcn_readfirstlane(bt)));
+    sl = block_slice<USE_LDS>(a, lds, b);
+    two = sl.nvec > 3 * GR_BLOCK;
+    if (USE_LDS) {
+      tr = sl.src[min((int)threadIdx.x, sl.nvec - 1)];
+      if (two) tr2 = sl.src[min((int)threadIdx.x + 3 * GR_BLOCK, sl.nvec - 1)];
+    }
+  };
   auto commit = [&]() {
     if (USE_LDS) {
       if ((int)threadIdx.x < sl.nvec) lds[threadIdx.x] = tr;
@@ -1206,6 +1243,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     if (USE_LDS || OBST) __syncthreads();
   };
 
+  if constexpr (!LOADS_FIRST) slice_loads();
   if (role == 0) {
     // ======================= physics waves =======================
     // SQUASH_HO: under the action lag the policy waves squash this step's action and hand it over.  The obstacle
@@ -1216,6 +1254,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     const bool handed = SQUASH_HO && lagged;
     Env e;
     load_env(a, ii, e);
+    if constexpr (LOADS_FIRST) slice_loads();
     const float dt = c.step_dt;
     const float v_prev[3] = {e.v[0], e.v[1], e.v[2]}, w_prev[3] = {e.w[0], e.w[1], e.w[2]};
     const float mar_prev = e.mar;
@@ -1429,9 +1468,14 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     RSTAMP(10);
   } else if (role == 1) {
     // ======================= policy-observation waves =======================
-    const uint32_t cnt = a.buf.counters[a.buf.counter_index];
+    // the call counter is read last of this wave's entry loads (below): its address needs two more kernarg words, and
+    // as a wave-uniform value read through a vector load it is waited for in full, which ahead of the other loads
+    // held each of them back by a round trip
+    uint32_t cnt;
+    if constexpr (!LOADS_FIRST) cnt = a.buf.counters[a.buf.counter_index];
     const int4 is = reinterpret_cast<const int4*>(a.buf.istate)[ii];
     const float4 r0 = reinterpret_cast<const float4*>(a.buf.state)[GR_P_RST0 * (size_t)n + ii];
+    if constexpr (LOADS_FIRST) slice_loads();
     Env e;
     e.ep = is.x; e.acc = is.y; e.epoch = is.z;
     e.gate = is.w & 0xff; e.lvl = (is.w >> 8) & 0xff; e.type = (is.w >> 24) & 0xff;
@@ -1459,6 +1503,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
       const int hfirst = __float_as_int(hint.x), hcount = __float_as_int(hint.y) - 1;
       float4 psp[GR_OBST_BATCH];  // cull spheres of the hinted list's first batch
       obst_spheres(a, hfirst, 0, hcount, psp);
+      if constexpr (LOADS_FIRST) cnt = a.buf.counters[a.buf.counter_index];
       STAMP(1);
       commit();  // barrier 1
       STAMP(2);
@@ -1480,6 +1525,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
       STAMP(12);
       obs_noise(a, gid, cnt, on);  // off the critical path: needed after barrier 2
     } else {
+      if constexpr (LOADS_FIRST) cnt = a.buf.counters[a.buf.counter_index];
       STAMP(15);
       commit();  // barrier 1 (joined at once: the physics and episode waves set its time)
       STAMP(1);
@@ -1524,6 +1570,7 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     const size_t ns = (size_t)n;
     const int4 is = reinterpret_cast<const int4*>(a.buf.istate)[ii];
     const float4 r0 = S[GR_P_RST0 * ns + ii], r1 = S[GR_P_RST1 * ns + ii], p2 = S[GR_P_PAR2 * ns + ii];
+    if constexpr (LOADS_FIRST) slice_loads();
     Env e;
     e.ep = is.x; e.acc = is.y; e.epoch = is.z;
     e.gate = is.w & 0xff; e.lvl = (is.w >> 8) & 0xff; e.type = (is.w >> 24) & 0xff;
@@ -1531,14 +1578,21 @@ __global__ GR_STEP_LB void step_kernel(KArgs a, const KConst* __restrict__ kc,
     e.k2[2] = r1.x; e.k1[0] = r1.y; e.k1[1] = r1.z; e.k1[2] = r1.w;
     e.mc = p2.w;
     // the next episode's start state, for every env (only the resetting ones use it)
+    ResetCfg rc{};
+    if constexpr (LOADS_FIRST) rc = reset_cfg(c);
     ResetDraws rd;
     reset_draws(a, gid, (uint32_t)e.epoch + 1u, e.mc, rd);
+    if constexpr (LOADS_FIRST)
+      __asm__ volatile("" : "+s"(rc.level_up_threshold), "+s"(rc.level_down_threshold), "+s"(rc.noise_curriculum),
+                       "+s"(rc.noise_enhance_threshold), "+s"(rc.noise_decay_threshold), "+s"(rc.num_levels),
+                       "+s"(rc.random_drag), "+s"(rc.noise_enhance), "+s"(rc.noise_decay));
     STAMP(1);
     commit();  // barrier 1 (the start gate of the next episode's track is read from the slice)
     STAMP(2);
     {
       Env er = e;
-      reset_apply(a, sl.tab, er, rd);
+      if constexpr (LOADS_FIRST) reset_apply(rc, sl.tab, er, rd);
+      else reset_apply(c, sl.tab, er, rd);
       float4* xr = xch + GR_XF4 * GR_BLOCK;
       xr[R_POSQ * GR_BLOCK + t] = make_float4(er.p[0], er.p[1], er.p[2], er.q[0]);
       xr[R_QV * GR_BLOCK + t] = make_float4(er.q[1], er.q[2], er.q[3], er.v[0]);

@@ -10,6 +10,7 @@ Stamps of the step kernel (lane 0 of each wave, s_memtime shader cycles; 9/10 s_
   observation waves: 0 entry, 1 loads + obs noise, 2 table barrier, 6 reset draws,
                      7 barrier 2 + resets + gate progress, 8 observations + log rows
   policy waves, gate-only tracks: 15 arrival at the table barrier
+  first state loads issued (not returned): 6 in the physics and policy waves, 7 in the episode waves
 """
 import json
 import os
@@ -29,6 +30,7 @@ def build():
     build_patched.build("stamps", [], "-DGR_STAMPS")
 
 
+FIRST_LOAD = {"physics": 6, "policy": 6, "episode": 7}  # GR_STAMP_FIRST_LOAD of gr_kernels.hip
 ROLE_PHASES = {
     "physics": [("loads+integrate", 0, 3), ("barrier1", 3, 14), ("gate_collision", 14, 15),
                 ("obstacle_wait", 15, 4), ("termination+handover", 4, 5),
@@ -111,6 +113,20 @@ def run(n=int(os.environ.get("N", "65536")), steps=200):
     rel = st[role == 0][:, 14] - wg_t0[role == 0]
     b1["physics_released"] = [float(np.percentile(rel, q)) for q in (10, 50, 90)]
     out["barrier1_cycles_after_workgroup_entry p10/p50/p90"] = b1
+    # each role's first state loads issued (FIRST_LOAD) and its arrival at barrier 2 (the stamp before it), same clock
+    b2_arrive = {"physics": 5, "policy": 12 if obst else 2, "episode": 6}
+    for key, slots in (("first_load_issued", FIRST_LOAD), ("barrier2_arrival", b2_arrive)):
+        res = {}
+        for r, name in enumerate(("physics", "policy", "episode")):
+            sel = role == r
+            ok = (st[sel][:, slots[name]] != 0).all()  # (a build without that stamp)
+            res[name] = [float(np.percentile(st[sel][:, slots[name]] - wg_t0[sel], q)) for q in (10, 50, 90)] if ok else None
+        if key == "barrier2_arrival":
+            last2 = np.stack([st[role == r][:, slots[nm]].reshape(-1, 4).max(axis=1) for r, nm in
+                              enumerate(("physics", "policy", "episode"))], axis=1)
+            res["last_to_arrive_share"] = {nm: float((last2.argmax(axis=1) == j).mean())
+                                           for j, nm in enumerate(("physics", "policy", "episode"))}
+        out[key + "_cycles_after_workgroup_entry p10/p50/p90"] = res
     for r, name in enumerate(("physics", "policy", "episode")):
         sel = st[role == r]
         life = sel[:, 8] - sel[:, 0]
