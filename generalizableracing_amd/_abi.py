@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 11
+GR_ABI_VERSION = 12
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -369,6 +369,13 @@ SIGNATURES = {
     "gr_gru_seq_forward": (C.c_int, [vp, i64, i64, vp, vp, i64] + [vp] * 4 + [i32, i64, i32, i32, vp, vp, vp]),
     # (gout, x, ldx_t, ldx_b, h0, dones, ld_dones, w_hh, out, gates, t, b, d, R, scratch, grads, stream)
     "gr_gru_seq_backward": (C.c_int, [vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp]),
+    # the wide family (d <= 256): the same argument lists, the scratch query with d, the backward with w_ih before w_hh
+    # and (gx, ldgx_t, ldgx_b) before stream
+    "gr_gru_wide_scratch_floats": (i64, [i64, i64, i32, i32]),
+    "gr_gru_wide_step": (C.c_int, [vp, i64, vp, vp] + [vp] * 4 + [i64, i32, i32, vp]),
+    "gr_gru_wide_seq_forward": (C.c_int, [vp, i64, i64, vp, vp, i64] + [vp] * 4 + [i32, i64, i32, i32, vp, vp, vp]),
+    "gr_gru_wide_seq_backward": (C.c_int, [vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, i32, i64, i32, i32, vp, vp,
+                                           vp, i64, i64, vp]),
     "gr_offline_scratch_ints": (i64, [i64]),
     # (feat, ld, aux, ld, n, d, features, supervision, capacity, cursor, scratch, stream)
     "gr_offline_collect": (C.c_int, [vp, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp]),

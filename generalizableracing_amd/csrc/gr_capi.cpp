@@ -1247,7 +1247,7 @@ int gr_gru_step(const float* x, int64_t ldx, float* h, float* h_prev_out, const 
       !aligned16(h) || !aligned16(h_prev_out) || !aligned16(w_hh) || !aligned16(b_ih) || !aligned16(b_hh))
     return GR_ERR_ARG;
   const hipError_t e = gr::launch_gru_forward(x, 0, ldx, h, nullptr, 0, w_ih, w_hh, b_ih, b_hh, 1, n, d, r, h,
-                                              nullptr, h_prev_out, (hipStream_t)stream);
+                                              nullptr, h_prev_out, false, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
@@ -1259,7 +1259,7 @@ int gr_gru_seq_forward(const float* x, int64_t ldx_t, int64_t ldx_b, const float
       !aligned16(b_hh) || !aligned16(out) || !aligned16(gates))
     return GR_ERR_ARG;
   const hipError_t e = gr::launch_gru_forward(x, ldx_t, ldx_b, h0, dones, ld_dones, w_ih, w_hh, b_ih, b_hh, t, b, d, r,
-                                              out, gates, nullptr, (hipStream_t)stream);
+                                              out, gates, nullptr, false, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 
@@ -1272,7 +1272,55 @@ int gr_gru_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_
       !aligned16(gates) || !aligned16(scratch) || !aligned16(grads))
     return GR_ERR_ARG;
   const hipError_t e = gr::launch_gru_backward(gout, x, ldx_t, ldx_b, h0, dones, ld_dones, w_hh, out, gates, t, b, d,
-                                               r, scratch, grads, (hipStream_t)stream);
+                                               r, scratch, grads, nullptr, nullptr, 0, 0, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+// the wide family: the same limits with d <= 256
+static bool gru_wide_sizes_ok(int64_t t, int64_t b, int32_t d, int32_t r) {
+  return d >= 1 && d <= 256 && gru_sizes_ok(t, b, 1, r);
+}
+
+int64_t gr_gru_wide_scratch_floats(int64_t t, int64_t b, int32_t d, int32_t r) {
+  if (!gru_wide_sizes_ok(t, b, d, r)) return GR_ERR_ARG;
+  return gr::gru_wide_scratch_floats(t, b, d, r);
+}
+
+int gr_gru_wide_step(const float* x, int64_t ldx, float* h, float* h_prev_out, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, int64_t n, int32_t d, int32_t r, void* stream) {
+  if (!gru_wide_sizes_ok(1, n, d, r) || ldx < d || !x || !h || !w_ih || !w_hh || !b_ih || !b_hh || h_prev_out == h ||
+      !aligned16(h) || !aligned16(h_prev_out) || !aligned16(w_hh) || !aligned16(b_ih) || !aligned16(b_hh))
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_forward(x, 0, ldx, h, nullptr, 0, w_ih, w_hh, b_ih, b_hh, 1, n, d, r, h,
+                                              nullptr, h_prev_out, false, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+int gr_gru_wide_seq_forward(const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0, const uint8_t* dones,
+                            int64_t ld_dones, const float* w_ih, const float* w_hh, const float* b_ih,
+                            const float* b_hh, int32_t t, int64_t b, int32_t d, int32_t r, float* out, float* gates,
+                            void* stream) {
+  if (!gru_wide_sizes_ok(t, b, d, r) || ldx_b < d || ldx_t < 0 || ld_dones < 0 || !x || !h0 || !dones || !w_ih ||
+      !w_hh || !b_ih || !b_hh || !out || out == h0 || !aligned16(h0) || !aligned16(w_hh) || !aligned16(b_ih) ||
+      !aligned16(b_hh) || !aligned16(out) || !aligned16(gates))
+    return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_forward(x, ldx_t, ldx_b, h0, dones, ld_dones, w_ih, w_hh, b_ih, b_hh, t, b, d, r,
+                                              out, gates, nullptr, true, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+int gr_gru_wide_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0,
+                             const uint8_t* dones, int64_t ld_dones, const float* w_ih, const float* w_hh,
+                             const float* out, const float* gates, int32_t t, int64_t b, int32_t d, int32_t r,
+                             float* scratch, float* grads, float* gx, int64_t ldgx_t, int64_t ldgx_b, void* stream) {
+  if (!gru_wide_sizes_ok(t, b, d, r) || ldx_b < d || ldx_t < 0 || ld_dones < 0 || !gout || !x || !h0 || !dones ||
+      !w_ih || !w_hh || !out || !gates || !scratch || !grads || !aligned16(gout) || !aligned16(h0) ||
+      !aligned16(out) || !aligned16(gates) || !aligned16(scratch) || !aligned16(grads))
+    return GR_ERR_ARG;
+  // gx rows must not overlap: t-major blocks of b rows of at least d floats
+  if (gx && (ldgx_b < d || (t > 1 && ldgx_t / b < ldgx_b))) return GR_ERR_ARG;
+  const hipError_t e = gr::launch_gru_backward(gout, x, ldx_t, ldx_b, h0, dones, ld_dones, w_hh, out, gates, t, b, d,
+                                               r, scratch, grads, w_ih, gx, ldgx_t, ldgx_b, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
 }
 

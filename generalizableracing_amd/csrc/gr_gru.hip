@@ -16,6 +16,16 @@
 //           gradients [da_r | da_z | da_n | da_hn] per (t, env) and streams W_hh's columns for dh' = z dh + W_hh^T da.
 // gru_wgrad / gru_final : gW_ih = sum da_i^T x, gW_hh = sum da_h^T h', the biases their column sums, over row splits
 //           into partial rows, summed in a fixed order (partial_rows_sum).  No atomics: bit-reproducible.
+// The wide family (gr_gru_wide_*: d <= 256, and the input gradient) runs the same gru_fwd and gru_bwd (their input loop
+// and their arithmetic do not depend on d's range) and adds
+// gru_gi      : the sequence's input projection hoisted out of the serial loop, gi [T B][3R] = x W_ih^T, as the very
+//           MFMA chain gru_fwd's input loop runs (same operands, same k order, from zero), written into the gates
+//           buffer's own r, z, n slots; gru_fwd<R, true> then starts its accumulators from them.  The same bits as the
+//           in-loop form (which the rollout step keeps: it has no serial loop to hoist from), one device-wide GEMM
+//           instead of 3R x d more weights streamed per step per workgroup.
+// gru_wgrad_x : gW_ih's columns past gru_wgrad's four tiles, the same row splits and partial rows;
+// gru_gx      : gx [T B][d] = da_i [T B][3R] W_ih [3R][d], one fixed-order MFMA chain over the 3R gate units per
+//           output, so a row's gx does not depend on the rows around it.
 // The MFMA fragment convention and helpers: gr_mfma.h.
 #include <hip/hip_runtime.h>
 
@@ -50,7 +60,8 @@ struct FwdArgs {
   int T, B, D;
 };
 
-template <int R>
+// GI: the input part of a_r, a_z, a_n was computed by gru_gi and lies in the step's gates row (its r, z, n slots)
+template <int R, bool GI = false>
 __global__ __launch_bounds__(R * 4) void gru_fwd(FwdArgs a) {
   constexpr int Q = R / 16, HP = R + 4, NTH = R * 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
@@ -82,20 +93,26 @@ __global__ __launch_bounds__(R * 4) void gru_fwd(FwdArgs a) {
     float* hw = lds + ((t + 1) & 1) * GE * HP;
     m4 ar = zero4(), az = zero4(), ani = zero4(), anh = zero4();
     // ---- input part: k = input 16 q + 4 g + r (inputs past D: 0)
-    const float* xr = a.x + (size_t)t * a.ldx_t + (size_t)bb * a.ldx_b;
-    for (int q = 0; q < DQ; ++q) {
+    if constexpr (GI) {
+      // (the lane's own slots of the row: read here, overwritten with the gates below)
+      const float* gp = a.gates + ((size_t)t * B + bb) * (4 * R) + uc;
+      ar = ld4(gp), az = ld4(gp + R), ani = ld4(gp + 2 * R);
+    } else {
+      const float* xr = a.x + (size_t)t * a.ldx_t + (size_t)bb * a.ldx_b;
+      for (int q = 0; q < DQ; ++q) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k = 16 * q + 4 * g + r;
-        const bool ok = k < D;
-        const int kk = ok ? k : 0;
-        const float xv = ok ? xr[kk] : 0.0f;
-        const float wr = wih[(size_t)(u0 + j) * D + kk];
-        const float wz = wih[(size_t)(R + u0 + j) * D + kk];
-        const float wn = wih[(size_t)(2 * R + u0 + j) * D + kk];
-        ar = mf(ok ? wr : 0.0f, xv, ar);
-        az = mf(ok ? wz : 0.0f, xv, az);
-        ani = mf(ok ? wn : 0.0f, xv, ani);
+        for (int r = 0; r < 4; ++r) {
+          const int k = 16 * q + 4 * g + r;
+          const bool ok = k < D;
+          const int kk = ok ? k : 0;
+          const float xv = ok ? xr[kk] : 0.0f;
+          const float wr = wih[(size_t)(u0 + j) * D + kk];
+          const float wz = wih[(size_t)(R + u0 + j) * D + kk];
+          const float wn = wih[(size_t)(2 * R + u0 + j) * D + kk];
+          ar = mf(ok ? wr : 0.0f, xv, ar);
+          az = mf(ok ? wz : 0.0f, xv, az);
+          ani = mf(ok ? wn : 0.0f, xv, ani);
+        }
       }
     }
     // ---- hidden part: k step 4 q + r = unit 16 q + 4 g + r of h'
@@ -139,6 +156,54 @@ __global__ __launch_bounds__(R * 4) void gru_fwd(FwdArgs a) {
       }
     }
     __syncthreads();  // the step's h' complete; every wave is done reading the other buffer
+  }
+}
+
+constexpr int GI_CT = 4;     // gru_gi: 16-row column tiles per workgroup
+constexpr int GI_WAVES = 4;  // one 16-row tile of W_ih's 3R rows per wave
+
+// gi = x W_ih^T into the gates buffer: element (row, m < 3R) at gates[row 4R + m].  blockIdx.x: GI_CT tiles of 16 rows
+// (t, b), blockIdx.y: 64 of the 3R gate units.  A = W_ih row m0 + j, B = x^T (column j = the row), k = input
+// 16 q + 4 g + r, inputs past D: 0 -- gru_fwd's input loop operand for operand, so each output is the same chain.
+template <int R>
+__global__ __launch_bounds__(GI_WAVES * 64) void gru_gi(FwdArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
+  const int B = a.B, D = a.D;
+  const int DQ = (D + 15) >> 4;
+  const int rows = a.T * B;
+  const int m0 = 16 * (blockIdx.y * GI_WAVES + wave);  // < 3R
+  const int row0 = blockIdx.x * (16 * GI_CT);
+  const float* xr[GI_CT];
+#pragma unroll
+  for (int c = 0; c < GI_CT; ++c) {
+    const int row = row0 + 16 * c + j;
+    const int rr = row < rows ? row : rows - 1;
+    const int t = rr / B, bq = rr - t * B;
+    xr[c] = a.x + (size_t)t * a.ldx_t + (size_t)bq * a.ldx_b;
+  }
+  const float* wr = a.w_ih + (size_t)(m0 + j) * D;
+  m4 acc[GI_CT];
+#pragma unroll
+  for (int c = 0; c < GI_CT; ++c) acc[c] = zero4();
+  for (int q = 0; q < DQ; ++q) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int k = 16 * q + 4 * g + r;
+      const bool ok = k < D;
+      const int kk = ok ? k : 0;
+      const float w = wr[kk];
+      const float wv = ok ? w : 0.0f;
+#pragma unroll
+      for (int c = 0; c < GI_CT; ++c) {
+        const float xv = xr[c][kk];
+        acc[c] = mf(wv, ok ? xv : 0.0f, acc[c]);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < GI_CT; ++c) {
+    const int row = row0 + 16 * c + j;
+    if (row < rows) st4(a.gates + (size_t)row * (4 * R) + m0 + 4 * g, acc[c]);
   }
 }
 
@@ -315,6 +380,120 @@ __global__ __launch_bounds__(WG_WAVES * 64) void gru_wgrad(WgArgs a) {
   }
 }
 
+// gW_ih's columns 64 (blockIdx.z + 1) .. + 63 (the wide family, d > 64): gru_wgrad's input part on the next four
+// column tiles, into the same partial rows (gru_wgrad wrote the first four, gW_hh and the biases)
+template <int R>
+__global__ __launch_bounds__(WG_WAVES * 64) void gru_wgrad_x(WgArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
+  const int B = a.B, D = a.D;
+  const int k0 = 64 * (blockIdx.z + 1);                // < D
+  const int m0 = 16 * (blockIdx.x * WG_WAVES + wave);  // < 3R
+  const int rows = a.T * B;
+  const int lo = blockIdx.y * a.rows_per_split;
+  const int hi = lo + a.rows_per_split < rows ? lo + a.rows_per_split : rows;
+  m4 ai[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ai[q] = zero4();
+  for (int s = lo; s < hi; s += 4) {
+    const int row = s + g;
+    const bool ok = row < hi;
+    const int rr = ok ? row : lo;
+    const int t = rr / B, bq = rr - t * B;
+    const float gi = a.ga[(size_t)rr * (4 * R) + m0 + j];
+    const float avi = ok ? gi : 0.0f;
+    const float* xr = a.x + (size_t)t * a.ldx_t + (size_t)bq * a.ldx_b;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = k0 + 16 * q + j;
+      const float xv = k < D ? xr[k < D ? k : 0] : 0.0f;
+      ai[q] = mf(avi, xv, ai[q]);
+    }
+  }
+  float* pih = a.part + (size_t)blockIdx.y * (size_t)grad_floats(R, D);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int m = m0 + 4 * g + q;
+#pragma unroll
+    for (int dq = 0; dq < 4; ++dq)
+      if (k0 + 16 * dq + j < D) pih[(size_t)m * D + k0 + 16 * dq + j] = ai[dq][q];
+  }
+}
+
+struct GxArgs {
+  const float* ga;    // [rows][4R]: da_r, da_z, da_n first
+  const float* w_ih;  // [3R][D]
+  float* gx;          // row (t, b), input k at gx[t ld_t + b ld_b + k]
+  long long ld_t, ld_b;
+  int rows, B, D;
+};
+
+constexpr int GX_RT = 4;     // 16-row tiles per workgroup
+constexpr int GX_WAVES = 4;  // wave w owns the column tiles w, w + 4, w + 8, w + 12 of all GX_RT row tiles
+
+// gx = da_i W_ih: A = da_i (row j of a row tile, k order: a float4 of 4 consecutive gate units feeds 4 k steps),
+// B = W_ih[gate unit][input 16 ct + j], C rows = rows 4 g + r of the tile, column = the input.  Every output is one
+// chain over the gate units 0 .. 3R - 1 in this order whatever the launch holds.
+template <int R>
+__global__ __launch_bounds__(GX_WAVES * 64) void gru_gx(GxArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, j = lane & 15;
+  const int D = a.D, rows = a.rows;
+  const int DQ = (D + 15) >> 4;
+  const int row0 = blockIdx.x * (16 * GX_RT);
+  const float* ap[GX_RT];
+#pragma unroll
+  for (int rt = 0; rt < GX_RT; ++rt) {
+    const int r = row0 + 16 * rt + j;
+    ap[rt] = a.ga + (size_t)(r < rows ? r : rows - 1) * (4 * R) + 4 * g;
+  }
+  int col[4];
+  bool cok[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int k = 16 * (wave + GX_WAVES * c) + j;
+    cok[c] = k < D;
+    col[c] = cok[c] ? k : 0;
+  }
+  m4 acc[GX_RT][4];
+#pragma unroll
+  for (int rt = 0; rt < GX_RT; ++rt)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[rt][c] = zero4();
+  const float* wih = a.w_ih;
+#pragma unroll 2
+  for (int q = 0; q < 3 * R / 16; ++q) {
+    m4 av[GX_RT];
+#pragma unroll
+    for (int rt = 0; rt < GX_RT; ++rt) av[rt] = ld4(ap[rt] + 16 * q);
+    const float* wq = wih + (size_t)(16 * q + 4 * g) * D;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (wave + GX_WAVES * c >= DQ) continue;  // (wave-uniform)
+      float w[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = wq[(size_t)r * D + col[c]];
+        w[r] = cok[c] ? v : 0.0f;
+      }
+#pragma unroll
+      for (int rt = 0; rt < GX_RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[rt][c] = mf(av[rt][r], w[r], acc[rt][c]);
+    }
+  }
+#pragma unroll
+  for (int rt = 0; rt < GX_RT; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + 16 * rt + 4 * g + r;
+      if (row >= rows) continue;
+      const int t = row / a.B, b = row - t * a.B;
+      float* o = a.gx + (size_t)t * a.ld_t + (size_t)b * a.ld_b;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (cok[c]) o[col[c]] = acc[rt][c][r];
+    }
+}
+
 // grads[e] = the fixed-order sum of the splits' partial rows: a lane owns 4 consecutive elements, the 4 waves take
 // every 4th partial row and are summed in wave order (as lcp_final)
 __global__ __launch_bounds__(GF_WAVES * 64) void gru_final(const float* __restrict__ part, int splits, long long ld,
@@ -349,17 +528,35 @@ static void wgrad_split(long long rows, int r, int* rows_per_split, int* splits)
 }
 
 template <int R>
-static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t s) {
-  return launch_lds<gru_fwd<R>>(dim3(tiles(a.B)), dim3(R * 4), (size_t)4 * 2 * GE * (R + 4), s, a);
+static hipError_t launch_fwd_t(const FwdArgs& a, bool hoist, hipStream_t s) {
+  if (!hoist) return launch_lds<gru_fwd<R>>(dim3(tiles(a.B)), dim3(R * 4), (size_t)4 * 2 * GE * (R + 4), s, a);
+  const int rows = a.T * a.B;
+  hipLaunchKernelGGL(gru_gi<R>, dim3((rows + 16 * GI_CT - 1) / (16 * GI_CT), 3 * R / (16 * GI_WAVES)),
+                     dim3(GI_WAVES * 64), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_lds<gru_fwd<R, true>>(dim3(tiles(a.B)), dim3(R * 4), (size_t)4 * 2 * GE * (R + 4), s, a);
 }
 
 template <int R>
-static hipError_t launch_bwd_t(const BwdArgs& a, const WgArgs& w, int splits, float* grads, hipStream_t s) {
+static hipError_t launch_bwd_t(const BwdArgs& a, const WgArgs& w, int splits, float* grads, const GxArgs* gx,
+                               hipStream_t s) {
   hipError_t e = launch_lds<gru_bwd<R>>(dim3(tiles(a.B)), dim3(R * 4), (size_t)4 * 2 * GE * (3 * R + 4), s, a);
   if (e != hipSuccess) return e;
+  if (gx) {  // (the wide family only)
+    hipLaunchKernelGGL(gru_gx<R>, dim3((gx->rows + 16 * GX_RT - 1) / (16 * GX_RT)), dim3(GX_WAVES * 64), 0, s, *gx);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(gru_wgrad<R>, dim3(3 * R / (16 * WG_WAVES), splits), dim3(WG_WAVES * 64), 0, s, w);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
+  if (w.D > 64) {  // (the wide family only)
+    hipLaunchKernelGGL(gru_wgrad_x<R>, dim3(3 * R / (16 * WG_WAVES), splits, (w.D - 1) / 64),
+                       dim3(WG_WAVES * 64), 0, s, w);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
   const long long ld = grad_floats(R, w.D);
   hipLaunchKernelGGL(gru_final, dim3((unsigned)((ld / 4 + 63) / 64)), dim3(GF_WAVES * 64), 0, s,
                      (const float*)w.part, splits, ld, grads);
@@ -375,27 +572,35 @@ int64_t gru_scratch_floats(long long t, long long b, int r) {
   return t * b * 4 * r + (int64_t)splits * gru::grad_floats(r, 64);
 }
 
+// the same of gr_gru_wide_seq_backward (d <= 256)
+int64_t gru_wide_scratch_floats(long long t, long long b, int d, int r) {
+  int rps, splits;
+  gru::wgrad_split(t * b, r, &rps, &splits);
+  return t * b * 4 * r + (int64_t)splits * gru::grad_floats(r, d);
+}
+
 hipError_t launch_gru_forward(const float* x, long long ldx_t, long long ldx_b, const float* h0,
                               const unsigned char* dones, long long ld_dones, const float* w_ih, const float* w_hh,
                               const float* b_ih, const float* b_hh, int t, long long b, int d, int r, float* out,
-                              float* gates, float* h_prev_out, hipStream_t s) {
+                              float* gates, float* h_prev_out, bool hoist, hipStream_t s) {
   gru::FwdArgs a = {};
   a.x = x, a.ldx_t = ldx_t, a.ldx_b = ldx_b, a.h0 = h0, a.dones = dones, a.ld_dones = ld_dones;
   a.w_ih = w_ih, a.w_hh = w_hh, a.b_ih = b_ih, a.b_hh = b_hh;
   a.out = out, a.gates = gates, a.h_prev_out = h_prev_out;
   a.T = t, a.B = (int)b, a.D = d;
+  hoist = hoist && gates && t > 1;  // (gi lives in the gates buffer; one step has no serial loop to hoist from)
   switch (r) {
-    case 64: return gru::launch_fwd_t<64>(a, s);
-    case 128: return gru::launch_fwd_t<128>(a, s);
-    case 192: return gru::launch_fwd_t<192>(a, s);
-    default: return gru::launch_fwd_t<256>(a, s);
+    case 64: return gru::launch_fwd_t<64>(a, hoist, s);
+    case 128: return gru::launch_fwd_t<128>(a, hoist, s);
+    case 192: return gru::launch_fwd_t<192>(a, hoist, s);
+    default: return gru::launch_fwd_t<256>(a, hoist, s);
   }
 }
 
 hipError_t launch_gru_backward(const float* gout, const float* x, long long ldx_t, long long ldx_b, const float* h0,
                                const unsigned char* dones, long long ld_dones, const float* w_hh, const float* out,
                                const float* gates, int t, long long b, int d, int r, float* scratch, float* grads,
-                               hipStream_t s) {
+                               const float* w_ih, float* gx, long long ldgx_t, long long ldgx_b, hipStream_t s) {
   gru::BwdArgs a = {};
   a.gout = gout, a.h0 = h0, a.out = out, a.gates = gates, a.dones = dones, a.ld_dones = ld_dones, a.w_hh = w_hh;
   a.ga = scratch, a.T = t, a.B = (int)b;
@@ -404,11 +609,15 @@ hipError_t launch_gru_backward(const float* gout, const float* x, long long ldx_
   gru::wgrad_split(t * b, r, &w.rows_per_split, &splits);
   w.ga = scratch, w.x = x, w.ldx_t = ldx_t, w.ldx_b = ldx_b, w.h0 = h0, w.out = out, w.dones = dones;
   w.ld_dones = ld_dones, w.part = scratch + (size_t)t * b * 4 * r, w.T = t, w.B = (int)b, w.D = d;
+  gru::GxArgs x_ = {};
+  x_.ga = scratch, x_.w_ih = w_ih, x_.gx = gx, x_.ld_t = ldgx_t, x_.ld_b = ldgx_b;
+  x_.rows = (int)(t * b), x_.B = (int)b, x_.D = d;
+  const gru::GxArgs* gp = gx ? &x_ : nullptr;
   switch (r) {
-    case 64: return gru::launch_bwd_t<64>(a, w, splits, grads, s);
-    case 128: return gru::launch_bwd_t<128>(a, w, splits, grads, s);
-    case 192: return gru::launch_bwd_t<192>(a, w, splits, grads, s);
-    default: return gru::launch_bwd_t<256>(a, w, splits, grads, s);
+    case 64: return gru::launch_bwd_t<64>(a, w, splits, grads, gp, s);
+    case 128: return gru::launch_bwd_t<128>(a, w, splits, grads, gp, s);
+    case 192: return gru::launch_bwd_t<192>(a, w, splits, grads, gp, s);
+    default: return gru::launch_bwd_t<256>(a, w, splits, grads, gp, s);
   }
 }
 

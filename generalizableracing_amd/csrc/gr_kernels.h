@@ -224,14 +224,17 @@ hipError_t launch_lcp_backward(const float* mu, long long ld_mu, const float* ac
                                float* grads, hipStream_t s);
 // gr_gru.hip: the GRU memory's masked sequence (T = 1: the rollout step), its BPTT and the backward's scratch
 int64_t gru_scratch_floats(long long t, long long b, int r);
+int64_t gru_wide_scratch_floats(long long t, long long b, int d, int r);
 hipError_t launch_gru_forward(const float* x, long long ldx_t, long long ldx_b, const float* h0,
                               const unsigned char* dones, long long ld_dones, const float* w_ih, const float* w_hh,
                               const float* b_ih, const float* b_hh, int t, long long b, int d, int r, float* out,
-                              float* gates, float* h_prev_out, hipStream_t s);
+                              float* gates, float* h_prev_out, bool hoist, hipStream_t s);
+// (hoist: the wide family's sequence, the input projection as one GEMM ahead of the serial kernel, into `gates`)
 hipError_t launch_gru_backward(const float* gout, const float* x, long long ldx_t, long long ldx_b, const float* h0,
                                const unsigned char* dones, long long ld_dones, const float* w_hh, const float* out,
                                const float* gates, int t, long long b, int d, int r, float* scratch, float* grads,
-                               hipStream_t s);
+                               const float* w_ih, float* gx, long long ldgx_t, long long ldgx_b, hipStream_t s);
+// (w_ih, gx, ldgx_*: the wide family's input gradient; gx null: none)
 hipError_t launch_in_backward(const float* gh, const float* hv, const float* x, long long m, int d, int ldx, int h,
                               float slope, float* part, float* sums, hipStream_t s);
 // Camera launch (camera_kernel, gr_camera.hip).  Dynamic LDS: the normal table and the ray tables (workgroup), then

@@ -53,6 +53,8 @@ _VISION = dict(
     entry_point="generalizableracing_amd.envs.racing_env:RacingEnv",
     env_cfg_entry_point="generalizableracing_amd.envs.racing_cfg:RacingVisionEnvCfg",
     rsl_rl_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterVisionPPORunnerCfg",
+    # PPO over the recurrent vision policy (VisionActorCriticRecurrent, rsl_rl_ppo_cfg.py:64-76)
+    rsl_rl_recurrent_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterVisionRecurrentPPORunnerCfg",
 )
 register("DiffLab-Quadcopter-CTBR-Racing-v0", **_VISION)
 # (round-3/4 name of the same pairing, kept as an alias)

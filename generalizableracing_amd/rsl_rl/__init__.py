@@ -12,3 +12,5 @@ from .rollout_storage_l2c2 import RolloutStorageL2C2  # noqa: F401
 from .vision_actor_critic import VisionActorCritic  # noqa: F401
 from .actor_critic_recurrent import ActorCriticRecurrent, Memory  # noqa: F401
 from .config import QuadcopterRecurrentPPORunnerCfg, RslRlPpoActorCriticRecurrentCfg  # noqa: F401
+from .vision_actor_critic_recurrent import VisionActorCriticRecurrent  # noqa: F401
+from .config import QuadcopterVisionRecurrentPPORunnerCfg, RslRlPpoVisionActorCriticRecurrentCfg  # noqa: F401

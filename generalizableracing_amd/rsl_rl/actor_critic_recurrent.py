@@ -110,20 +110,21 @@ class Memory(nn.Module):
         self.hidden_states.masked_fill_((dones.reshape(1, -1, 1) != 0).to(self.hidden_states.device), 0.0)
 
 
-class ActorCriticRecurrent(ActorCritic):
+class RecurrentHeads:
+    """What a policy with a memory in front of the actor and of the critic adds to its feed-forward base, shared by
+    ActorCriticRecurrent and VisionActorCriticRecurrent (mixed in ahead of the base).  `encode` maps observations
+    to the memories' inputs: the observations themselves here, the vision feature there."""
     is_recurrent = True
 
-    def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(256, 256, 256),
-                 critic_hidden_dims=(256, 256, 256), activation="elu", rnn_type="gru", rnn_hidden_size=256,
-                 rnn_num_layers=1, init_noise_std=1.0, noise_std_type: str = "scalar", fused_gru=True, **kwargs):
+    def init_memories(self, input_a, input_c, hidden_size, fused):
+        self.memory_a = Memory(input_a, hidden_size=hidden_size, fused=fused)
+        self.memory_c = Memory(input_c, hidden_size=hidden_size, fused=fused)
+
+    @staticmethod
+    def check_rnn(name, rnn_type, rnn_num_layers):
         if str(rnn_type).lower() != "gru" or int(rnn_num_layers) != 1:
-            raise NotImplementedError(f"ActorCriticRecurrent: rnn_type={rnn_type!r} with {rnn_num_layers} layer(s) is "
+            raise NotImplementedError(f"{name}: rnn_type={rnn_type!r} with {rnn_num_layers} layer(s) is "
                                       "not built; supported: rnn_type='gru' with rnn_num_layers=1")
-        super().__init__(rnn_hidden_size, rnn_hidden_size, num_actions, actor_hidden_dims=actor_hidden_dims,
-                         critic_hidden_dims=critic_hidden_dims, activation=activation, init_noise_std=init_noise_std,
-                         noise_std_type=noise_std_type, **kwargs)
-        self.memory_a = Memory(num_actor_obs, hidden_size=rnn_hidden_size, fused=fused_gru)
-        self.memory_c = Memory(num_critic_obs, hidden_size=rnn_hidden_size, fused=fused_gru)
 
     @property
     def fused_gru(self) -> bool:
@@ -148,13 +149,21 @@ class ActorCriticRecurrent(ActorCritic):
     def get_hidden_sizes(self):
         return self.memory_a.rnn.hidden_size, self.memory_c.rnn.hidden_size
 
+    def encode(self, observations):
+        """The memory's input for these observations ([N, .] in rollout mode, [T, B, .] in batch mode)."""
+        return observations
+
+    def memory_inputs(self, observations, critic_observations):
+        """(memory_a's, memory_c's) inputs for a mini-batch's [T, B, .] observation blocks (PPO._recurrent_loss)."""
+        return self.encode(observations), self.encode(critic_observations)
+
     def set_distribution(self, mean, draw=False):
         """The action distribution from the actor's output on the memory's rows; draw: sample once, as `act` does."""
         self.distribution = Normal(mean, self._std(mean))
         return self._sample() if draw else None
 
     def update_distribution(self, observations, masks=None, hidden_states=None):
-        self.set_distribution(self.actor(self.memory_a(observations, masks, hidden_states)))
+        self.set_distribution(self.actor(self.memory_a(self.encode(observations), masks, hidden_states)))
 
     def act(self, observations, masks=None, hidden_states=None):
         self.update_distribution(observations, masks, hidden_states)
@@ -168,7 +177,18 @@ class ActorCriticRecurrent(ActorCritic):
         return d.sample()
 
     def act_inference(self, observations):
-        return self.actor(self.memory_a(observations))
+        return self.actor(self.memory_a(self.encode(observations)))
 
     def evaluate(self, critic_observations, masks=None, hidden_states=None):
-        return self.critic(self.memory_c(critic_observations, masks, hidden_states))
+        return self.critic(self.memory_c(self.encode(critic_observations), masks, hidden_states))
+
+
+class ActorCriticRecurrent(RecurrentHeads, ActorCritic):
+    def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(256, 256, 256),
+                 critic_hidden_dims=(256, 256, 256), activation="elu", rnn_type="gru", rnn_hidden_size=256,
+                 rnn_num_layers=1, init_noise_std=1.0, noise_std_type: str = "scalar", fused_gru=True, **kwargs):
+        self.check_rnn("ActorCriticRecurrent", rnn_type, rnn_num_layers)
+        super().__init__(rnn_hidden_size, rnn_hidden_size, num_actions, actor_hidden_dims=actor_hidden_dims,
+                         critic_hidden_dims=critic_hidden_dims, activation=activation, init_noise_std=init_noise_std,
+                         noise_std_type=noise_std_type, **kwargs)
+        self.init_memories(num_actor_obs, num_critic_obs, rnn_hidden_size, fused_gru)

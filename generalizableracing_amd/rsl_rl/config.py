@@ -156,6 +156,36 @@ class RslRlPpoActorCriticRecurrentCfg(RslRlPpoActorCriticCfg):
 
 
 @dataclass
+class RslRlPpoVisionActorCriticRecurrentCfg(RslRlPpoActorCriticCfg):
+    """rsl_rl_ppo_cfg.py:64-76: the vision policy with a GRU memory (hidden size 192, one layer) between the 192-wide
+    feature and the heads [128, 128], lrelu."""
+
+    class_name: str = "VisionActorCriticRecurrent"
+    img_res: tuple = (72, 96)
+    dim_hidden_input: int = 192
+    rnn_type: str = "gru"
+    rnn_hidden_size: int = 192
+    rnn_num_layers: int = 1
+    actor_hidden_dims: list = field(default_factory=lambda: [128, 128])
+    critic_hidden_dims: list = field(default_factory=lambda: [128, 128])
+    # not in the reference: the memories through gr_gru_wide_* (rsl_rl/fused_gru.py); False keeps torch.nn.GRU
+    fused_gru: bool = True
+
+
+@dataclass
+class QuadcopterVisionRecurrentPPORunnerCfg(QuadcopterPPORunnerCfg):
+    """QuadcopterVisionPPORunnerCfg's algorithm block with class_name "PPO" (a recurrent policy is PPO only) over
+    VisionActorCriticRecurrent.  The reference defines the policy cfg (rsl_rl_ppo_cfg.py:64-76) but no runner cfg
+    that uses it: this pairing is this project's."""
+
+    max_iterations: int = 4000
+    experiment_name: str = "racing_ppo_vision_recurrent"
+    policy: RslRlPpoActorCriticCfg = field(default_factory=RslRlPpoVisionActorCriticRecurrentCfg)
+    algorithm: RslRlPpoAlgorithmCfg = field(
+        default_factory=lambda: RslRlPpoAlgorithmCfg(class_name="PPO", entropy_coef=0.005))
+
+
+@dataclass
 class QuadcopterRecurrentPPORunnerCfg(QuadcopterPPORunnerCfg):
     """QuadcopterPPORunnerCfg's algorithm block over ActorCriticRecurrent (a GRU memory before actor and critic)."""
 

@@ -4,6 +4,8 @@ Isaac Lab's export_policy_as_jit / export_policy_as_onnx used by standalone/rsl_
 * `export_policy_as_jit`: TorchScript of normalizer + actor MLP, input the 16-dim state obs.
 * `export_recurrent_policy_as_jit`: TorchScript of normalizer + GRU memory + actor for ActorCriticRecurrent,
   forward(obs [B,16], h_in [1,B,R]) -> (actions, h_out); the caller carries h and zeroes finished envs' rows.
+  For VisionActorCriticRecurrent the same call writes normalizer + stem (eval BatchNorm) + state encoder + GRU +
+  actor: forward(obs [B, 16 + 72*96], h_in [1,B,R]) -> (actions, h_out), obs the env's row (state, then the image).
 * `export_vision_policy_as_jit`: TorchScript of the vision policy with the reference exporter's
   two-input signature forward(state [B,16], depth_image [B,1,72,96]) -> actions
   (+ sigmoid(aux) when the auxiliary head is exported).
@@ -43,6 +45,30 @@ class _RecurrentPolicyExporter(nn.Module):
 
     def forward(self, obs: torch.Tensor, h_in: torch.Tensor):
         out, h_out = self.rnn(self.normalizer(obs).unsqueeze(0), h_in)
+        return self.actor(out.squeeze(0)), h_out
+
+
+class _VisionRecurrentPolicyExporter(nn.Module):
+    """exporter.py's recurrent branch for the vision policy: the feature of the env's row (state columns, then the
+    depth image), then the memory and the actor; the hidden state an explicit input and output."""
+
+    def __init__(self, policy, normalizer=None):
+        super().__init__()
+        self.stem = copy.deepcopy(policy.stem).cpu()
+        self.state_enc = copy.deepcopy(policy.state_enc).cpu()
+        self.activation = copy.deepcopy(policy.activation).cpu()
+        self.rnn = copy.deepcopy(policy.memory_a.rnn).cpu()
+        self.actor = copy.deepcopy(policy.actor).cpu()
+        self.normalizer = copy.deepcopy(normalizer).cpu() if normalizer is not None else nn.Identity()
+        self.img_h, self.img_w = int(policy.img_res[0]), int(policy.img_res[1])
+
+    def forward(self, obs: torch.Tensor, h_in: torch.Tensor):
+        x = self.normalizer(obs)
+        pixels = self.img_h * self.img_w
+        img = x[:, x.shape[1] - pixels:].reshape(-1, 1, self.img_h, self.img_w)
+        st = x[:, : x.shape[1] - pixels]
+        feat = self.activation(self.stem(img) + self.state_enc(st))
+        out, h_out = self.rnn(feat.unsqueeze(0), h_in)
         return self.actor(out.squeeze(0)), h_out
 
 
@@ -101,7 +127,8 @@ def export_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.
 
 def export_recurrent_policy_as_jit(policy, normalizer, path: str, filename: str = "policy.pt") -> str:
     os.makedirs(path, exist_ok=True)
-    m = _RecurrentPolicyExporter(policy, _normalizer(normalizer)).eval()
+    cls = _VisionRecurrentPolicyExporter if hasattr(policy, "stem") else _RecurrentPolicyExporter
+    m = cls(policy, _normalizer(normalizer)).eval()
     out = os.path.join(path, filename)
     torch.jit.script(m).save(out)
     return out

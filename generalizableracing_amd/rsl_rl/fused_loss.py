@@ -194,12 +194,14 @@ def ppo_loss(alg, obs, critic_obs, *batch, **sinks):
 
 def fused_losses_ok(policy, obs: torch.Tensor) -> bool:
     """rsl_rl's ActorCritic (state-independent std) with <= 8 actions, CUDA fp32 observations, outside autocast; for
-    ActorCriticRecurrent `obs` are its memory's output rows (PPO._recurrent_loss), the heads being the same MLPs."""
+    ActorCriticRecurrent and VisionActorCriticRecurrent `obs` are the memory's output rows (PPO._recurrent_loss), the
+    heads being the same MLPs."""
     from .actor_critic import ActorCritic
     from .actor_critic_recurrent import ActorCriticRecurrent
+    from .vision_actor_critic_recurrent import VisionActorCriticRecurrent
 
-    return (type(policy) in (ActorCritic, ActorCriticRecurrent) and obs.is_cuda and obs.dtype == torch.float32
-            and policy.actor[-1].out_features <= 8 and not torch.is_autocast_enabled("cuda"))
+    return (type(policy) in (ActorCritic, ActorCriticRecurrent, VisionActorCriticRecurrent) and obs.is_cuda
+            and obs.dtype == torch.float32 and policy.actor[-1].out_features <= 8 and not torch.is_autocast_enabled("cuda"))
 
 
 def ppo_losses(alg, obs, critic_obs, act, value_old, adv, ret, logp_old, mu_old, sig_old):

@@ -45,8 +45,8 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     pool (eager allocations between replays reused it and the replays' bias gradients came out wrong,
     scripts/debug_graph_update.py); and as a GEMM with a ones vector hipBLASLt tiles only the N x 1 output
     (1.5 ms at M = 393 216, N = 256, half of the update step)."""
-    if gy.device.type != "cuda":
-        return gy.float().sum(0)
+    if gy.device.type != "cuda":  # (a float64 policy, which the CPU golden tests step, keeps its precision)
+        return gy.sum(0) if gy.dtype == torch.float64 else gy.float().sum(0)
     lib = _abi.load()
     gy = gy.contiguous()
     m, n = gy.shape

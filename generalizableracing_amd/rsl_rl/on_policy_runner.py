@@ -25,10 +25,11 @@ from .ppo_l2c2 import PPOL2C2
 from .ppo_lcp import PPOLCP
 from .rollout_ops import EpisodeStats
 from .vision_actor_critic import VisionActorCritic
+from .vision_actor_critic_recurrent import VisionActorCriticRecurrent
 
 ALGORITHMS = {"PPO": PPO, "PPOL2C2": PPOL2C2, "PPOLCP": PPOLCP}
 POLICIES = {"ActorCritic": ActorCritic, "VisionActorCritic": VisionActorCritic,
-            "ActorCriticRecurrent": ActorCriticRecurrent}
+            "ActorCriticRecurrent": ActorCriticRecurrent, "VisionActorCriticRecurrent": VisionActorCriticRecurrent}
 
 
 class _CsvWriter:

@@ -317,13 +317,16 @@ class PPO:
 
     def _recurrent_loss(self, batch):
         """_minibatch_loss for a recurrent policy: `batch` as recurrent_mini_batch_generator yields it.  The memories
-        run over the [T, B] block (policy.act / evaluate with masks = the block's dones and hidden_states = its h0);
-        from the [T * B]-row memory outputs on, the feed-forward code runs unchanged on the policy's heads."""
+        run over the [T, B] block (policy.act / evaluate with masks = the block's dones and hidden_states = its h0) on
+        the inputs the policy forms from the observation blocks (memory_inputs: the blocks themselves for
+        ActorCriticRecurrent, the stem's features for VisionActorCriticRecurrent); from the [T * B]-row memory outputs
+        on, the feed-forward code runs unchanged on the policy's heads."""
         obs, critic_obs = batch[0], batch[1]
         (h0_a, h0_c), dones = batch[9], batch[10]
         pol = self.policy
-        feat_a = pol.memory_a(obs, dones, h0_a)
-        feat_c = pol.memory_c(critic_obs, dones, h0_c)
+        x_a, x_c = pol.memory_inputs(obs, critic_obs)
+        feat_a = pol.memory_a(x_a, dones, h0_a)
+        feat_c = pol.memory_c(x_c, dones, h0_c)
         rest = batch[2:9]
         # (the heads module by module: linear.networks_fusable refuses inputs that need a gradient, as these do)
         if self._use_fused_losses(feat_a):

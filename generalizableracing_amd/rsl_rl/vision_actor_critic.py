@@ -130,7 +130,9 @@ class VisionActorCritic(ActorCritic):
                  dim_hidden_input: int = 192, actor_hidden_dims=(256, 256, 256), critic_hidden_dims=(256, 256, 256),
                  activation="elu", init_noise_std=1.0, noise_std_type: str = "scalar", **kwargs):
         self.use_auxiliary_loss = bool(kwargs.pop("use_auxiliary_loss", False))
-        super().__init__(dim_hidden_input, dim_hidden_input, num_actions, actor_hidden_dims=actor_hidden_dims,
+        # the width the heads read: the feature's, or a subclass's memories' (VisionActorCriticRecurrent)
+        head_in = int(kwargs.pop("head_input_dim", dim_hidden_input))
+        super().__init__(head_in, head_in, num_actions, actor_hidden_dims=actor_hidden_dims,
                          critic_hidden_dims=critic_hidden_dims, activation=activation,
                          init_noise_std=init_noise_std, noise_std_type=noise_std_type, **kwargs)
         self.activation = resolve_nn_activation(activation)
@@ -174,7 +176,8 @@ class VisionActorCritic(ActorCritic):
             with torch.no_grad():
                 xd = x.detach().double()
                 stats = torch.stack([xd.mean(0), xd.var(0, unbiased=False), xd.var(0, unbiased=False),
-                                     xd.var(0, unbiased=True)]).float()
+                                     xd.var(0, unbiased=True)])
+                stats = stats if x.dtype == torch.float64 else stats.float()  # (a float64 policy keeps them)
             for _ in range(self._bn_uses - 1):  # (F.batch_norm made the first update)
                 if bn.num_batches_tracked is not None:
                     bn.num_batches_tracked.add_(1)

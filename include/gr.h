@@ -42,8 +42,8 @@ extern "C" {
  * 8: gr_offline_collect / gr_offline_pgd_step.  9: gr_stem_image / gr_bn_act in place of the stem entry points' and the
  * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit).  10: gr_mlp_net.h1mask
  * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired).  11: gr_gru_step, gr_gru_seq_forward,
- * gr_gru_seq_backward, gr_gru_scratch_floats */
-#define GR_ABI_VERSION 11
+ * gr_gru_seq_backward, gr_gru_scratch_floats.  12: the gr_gru_wide_* family (d <= 256, the input gradient) */
+#define GR_ABI_VERSION 12
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -689,6 +689,29 @@ int gr_gru_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_
                         const uint8_t* dones, int64_t ld_dones, const float* w_hh, const float* out,
                         const float* gates, int32_t t, int64_t b, int32_t d, int32_t r, float* scratch, float* grads,
                         void* stream);
+
+/* The wide family of the same memory, for VisionActorCriticRecurrent (its memories read the 192-wide feature, which
+ * trains: x needs a gradient).  The same kernels per step and the same contracts as the three above, with
+ * 1 <= d <= 256 (any d) and
+ *   gr_gru_wide_seq_backward: also gx, element (t, b, k) at gx[t ldgx_t + b ldgx_b + k] =
+ *                        W_ir^T da_r + W_iz^T da_z + W_in^T da_n (ldgx_b >= d, ldgx_t >= b ldgx_b; dense:
+ *                        ldgx_t = b d, ldgx_b = d); gx null: skipped.  h0 still gets no gradient.  Every gx row is one
+ *                        fixed-order MFMA chain over the 3R gate units: it does not depend on the rows around it.
+ * For d <= 64 the three shared outputs have the narrow family's bits.  scratch: gr_gru_wide_scratch_floats(t, b, d, R)
+ * floats (-1 for sizes not covered).  gr_gru_wide_seq_forward with gates not null and t > 1 computes the input
+ * projection x W_ih^T for all t b rows in one GEMM ahead of the serial kernel (staged in `gates`), as the same MFMA
+ * chains the in-loop form runs: the bits do not change, and gr_gru_wide_step iterated with resets still gives them. */
+int64_t gr_gru_wide_scratch_floats(int64_t t, int64_t b, int32_t d, int32_t r);
+int gr_gru_wide_step(const float* x, int64_t ldx, float* h, float* h_prev_out, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, int64_t n, int32_t d, int32_t r, void* stream);
+int gr_gru_wide_seq_forward(const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0, const uint8_t* dones,
+                            int64_t ld_dones, const float* w_ih, const float* w_hh, const float* b_ih,
+                            const float* b_hh, int32_t t, int64_t b, int32_t d, int32_t r, float* out, float* gates,
+                            void* stream);
+int gr_gru_wide_seq_backward(const float* gout, const float* x, int64_t ldx_t, int64_t ldx_b, const float* h0,
+                             const uint8_t* dones, int64_t ld_dones, const float* w_ih, const float* w_hh,
+                             const float* out, const float* gates, int32_t t, int64_t b, int32_t d, int32_t r,
+                             float* scratch, float* grads, float* gx, int64_t ldgx_t, int64_t ldgx_b, void* stream);
 
 /* The offline auxiliary-head stage (standalone/offline/data_collector.py, standalone/offline/train.py): a balanced
  * (feature, label) dataset kept on the device and the PGD-hardened fine-tune step of a Linear(d, 1) head on it.

@@ -12,6 +12,15 @@ update so every measurement times the same arithmetic.  Prints one JSON line per
 spread = (max - min) / median) and the torch / fused ratios, and writes every per-run value to --out.
 
     python scripts/time_gru.py [--rounds 7] [--reps 3] [--out profiles/gru_update_ab.json]
+
+The vision recipe's shape (VisionActorCriticRecurrent: the memories read the 192-wide feature, which trains):
+
+    python scripts/time_gru.py --input-width 192 --input-grad --vision-step   # -> profiles/gru_wide_update_ab.json
+
+    --input-width D   the memory legs on a [24, 1024, D] block of a [24, 4096, D] buffer (the wide family, D > 64)
+    --input-grad      seq_forward_backward also differentiates in x (gx)
+    --vision-step     the step leg is the whole recurrent vision mini-batch step (stem + state encoder on the rows of
+                      the storage's [24, 4096, 16 + 72 x 96] buffers, both memories, heads, losses, backward, clip, Adam)
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/time_gru.py --profile   # the fused step's kernels
                                                      # (profiles/gru_step_kernel_stats.csv is that run's stats file)
 """
@@ -28,7 +37,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from generalizableracing_amd.rsl_rl import PPO, ActorCriticRecurrent, fused_gru  # noqa: E402
+from generalizableracing_amd.rsl_rl import (PPO, ActorCriticRecurrent, VisionActorCriticRecurrent,  # noqa: E402
+                                            fused_gru)
+from generalizableracing_amd.rsl_rl.actor_critic_recurrent import Memory  # noqa: E402
 
 DEV = "cuda:0"
 N, T, NMB, OBS, K, R = 4096, 24, 4, 16, 4, 192
@@ -38,16 +49,25 @@ HP = dict(num_learning_epochs=1, num_mini_batches=NMB, clip_param=0.2, gamma=0.9
           desired_kl=0.01)
 
 
-def fill(alg, seed=0):
+def fill(alg, seed=0, pixels=0):
+    """One rollout of random rows: OBS state terms ~ N(0, 1), then `pixels` depth-like values in [0, 10] m."""
     g = torch.Generator(device="cpu").manual_seed(seed)
-    alg.init_storage("rl", N, T, [OBS], [OBS], [K])
+    gd = torch.Generator(device=DEV).manual_seed(seed)
+    width = OBS + pixels
+
+    def rows():
+        x = torch.randn(N, OBS, generator=g).to(DEV)
+        if pixels:
+            x = torch.cat([x, 10.0 * torch.rand(N, pixels, generator=gd, device=DEV)], dim=1)
+        return x
+
+    alg.init_storage("rl", N, T, [width], [width], [K])
     with torch.inference_mode():
         for _ in range(T):
-            obs, cobs = torch.randn(N, OBS, generator=g).to(DEV), torch.randn(N, OBS, generator=g).to(DEV)
-            alg.act(obs, cobs)
+            alg.act(rows(), rows())
             dones = (torch.rand(N, generator=g) < 0.02).to(DEV)
             alg.process_env_step((0.1 * torch.randn(N, generator=g)).to(DEV), dones, {})
-        alg.compute_returns(torch.randn(N, OBS, generator=g).to(DEV))
+        alg.compute_returns(rows())
 
 
 def stats(xs):
@@ -69,18 +89,31 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--profile", action="store_true", help="only a few fused update steps (under rocprofv3)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gru_update_ab.json"))
+    ap.add_argument("--input-width", type=int, default=OBS, help="input width D of the memory legs")
+    ap.add_argument("--input-grad", action="store_true", help="seq_forward_backward also differentiates in x")
+    ap.add_argument("--vision-step", action="store_true", help="the step leg on VisionActorCriticRecurrent")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_gru.py measures on the GPU"
+    D = a.input_width
+    wide = D != OBS or a.input_grad or a.vision_step
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "gru_wide_update_ab.json" if wide else "gru_update_ab.json")
     torch.manual_seed(0)
-    base = ActorCriticRecurrent(OBS, OBS, K, [128, 128], [128, 128], "lrelu", rnn_hidden_size=R).to(DEV)
+    pixels = 72 * 96 if a.vision_step else 0
+    if a.vision_step:
+        base = VisionActorCriticRecurrent(OBS + pixels, OBS + pixels, K, dim_hidden_input=192,
+                                          actor_hidden_dims=[128, 128], critic_hidden_dims=[128, 128],
+                                          activation="lrelu", rnn_hidden_size=R).to(DEV)
+    else:
+        base = ActorCriticRecurrent(OBS, OBS, K, [128, 128], [128, 128], "lrelu", rnn_hidden_size=R).to(DEV)
     variants = ("fused",) if a.profile else ("fused", "torch")
     algs, snaps = {}, {}
     for v in variants:
         pol = copy.deepcopy(base)
         pol.fused_gru = v == "fused"
         algs[v] = PPO(pol, device=DEV, **HP)
-        fill(algs[v])
+        fill(algs[v], pixels=pixels)
         snaps[v] = [p.detach().clone() for p in pol.parameters()]
 
     def update(v):
@@ -100,27 +133,39 @@ def main():
             update("fused")
         torch.cuda.synchronize()
         return
-    calls = fused_gru.CALLS
+    calls, wide_calls = fused_gru.CALLS, fused_gru.WIDE_CALLS
     update("fused")
     assert fused_gru.CALLS - calls == 2 * NMB, "the fused path was not taken"
+    assert fused_gru.WIDE_CALLS - wide_calls == (2 * NMB if a.vision_step else 0)
 
     # one memory over one mini-batch block, and one rollout step
     st = algs["fused"].storage
-    x, dones, h0 = st.observations[:T, :B], st.dones[:, :B, 0], st.h0_a[:B].unsqueeze(0)
+    dones, h0 = st.dones[:, :B, 0], st.h0_a[:B].unsqueeze(0)
+    if D == OBS and not a.vision_step:  # the policy's own memory on the stored observations
+        x = st.observations[:T, :B]
+        mems = {v: algs[v].policy.memory_a for v in variants}
+    else:  # a memory of input width D on a block of a [T, N, D] buffer
+        x = torch.randn(T, N, D, device=DEV)[:, :B]
+        ref = Memory(D, R).to(DEV)
+        mems = {v: copy.deepcopy(ref) for v in variants}
+        for v in variants:
+            mems[v].fused = v == "fused"
+    if a.input_grad:
+        x = x.detach().requires_grad_(True)
     gout = torch.randn(T * B, R, device=DEV)
-    xs, hs = torch.randn(N, OBS, device=DEV), {v: torch.zeros(1, N, R, device=DEV) for v in variants}
+    xs, hs = torch.randn(N, D, device=DEV), {v: torch.zeros(1, N, R, device=DEV) for v in variants}
 
     def seq_fwd(v):
         with torch.no_grad():
-            algs[v].policy.memory_a.sequence(x, dones, h0)
+            mems[v].sequence(x, dones, h0)
 
     def seq_fwd_bwd(v):
-        mem = algs[v].policy.memory_a
+        mem = mems[v]
         out = mem.sequence(x, dones, h0)
-        torch.autograd.grad(out, list(mem.parameters()), grad_outputs=gout)
+        torch.autograd.grad(out, list(mem.parameters()) + ([x] if a.input_grad else []), grad_outputs=gout)
 
     def rollout_step(v):
-        mem = algs[v].policy.memory_a
+        mem = mems[v]
         with torch.inference_mode():
             if v == "fused":
                 fused_gru.gru_step(mem.rnn, xs, hs[v][0])
@@ -151,6 +196,7 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump({"envs": N, "steps": T, "mini_batches": NMB, "envs_per_mini_batch": B, "hidden": R, "obs": OBS,
+                   "input_width": D, "input_grad": bool(a.input_grad), "step_policy": type(base).__name__,
                    "heads": [128, 128], "rounds": a.rounds, "reps_per_round": a.reps,
                    "unit": "us (host time ended by a device synchronise; step: update() / mini-batch steps; "
                            "seq_backward: forward + backward less forward)",

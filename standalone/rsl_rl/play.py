@@ -88,7 +88,7 @@ def main(argv=None):
     pol_mod = runner.alg.policy
     norm = runner.obs_normalizer
     exported = {}
-    if isinstance(pol_mod, VisionActorCritic):
+    if isinstance(pol_mod, VisionActorCritic) and not pol_mod.is_recurrent:
         exported["jit"] = exporter.export_vision_policy_as_jit(pol_mod, export_dir, norm, "vision_policy.pt")
         onnx_fn = lambda: exporter.export_vision_policy_as_onnx(  # noqa: E731
             pol_mod, export_dir, norm, "vision_policy.onnx", False, pol_mod.img_res, (16,))
