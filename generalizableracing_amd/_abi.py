@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 12
+GR_ABI_VERSION = 13
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -271,6 +271,14 @@ GR_POLICY_BF16, GR_POLICY_FP32 = 0, 1
 GR_POLICY_LRELU_PRESCALE = 0.505
 GR_CAM_STEP, GR_CAM_RESET, GR_CAM_OBSERVE = 0, 1, 2
 GR_DTYPE_F32, GR_DTYPE_BF16 = 0, 1
+# the RGB viewer (gr_view_render): modes, indices into the host `view` array, g-buffer planes and ids
+GR_VIEW_FPV, GR_VIEW_CHASE, GR_VIEW_FIXED = 0, 1, 2
+GR_VIEW_FLOATS = 16
+GR_VIEW_FX, GR_VIEW_FY, GR_VIEW_CX, GR_VIEW_CY, GR_VIEW_MAX_DISTANCE = range(5)
+GR_VIEW_CHASE_BACK, GR_VIEW_CHASE_UP, GR_VIEW_CHASE_AHEAD, GR_VIEW_EYE, GR_VIEW_TARGET = 5, 6, 7, 8, 11
+GR_VIEW_GBUF_WORDS = 5
+GR_VIEW_G_ID, GR_VIEW_G_DEPTH, GR_VIEW_G_NORMAL = 0, 1, 2
+GR_VIEW_ID_MISS, GR_VIEW_ID_GROUND, GR_VIEW_ID_DRONE = -1, 0, 1000000
 GR_STEP_L2, GR_STEP_LDS, GR_STEP_LDS8, GR_STEP_LDS8_LEAN, GR_STEP_OBST, GR_STEP_OBST_LEAN = range(6)
 STEP_KERNEL_NAMES = ["step_kernel<false, false>", "step_kernel<true, false>", "step_kernel<true, false, 8>",
                      "step_kernel<true, false, 8, 1>", "step_kernel<false, true>", "step_kernel<false, true, 0, 1>"]
@@ -325,6 +333,9 @@ SIGNATURES = {
     "gr_bind_camera_buffers": (C.c_int, [vp, C.POINTER(GrCameraBuffers)]),
     "gr_camera_render": (C.c_int, [vp, C.c_int, vp, vp]),
     "gr_camera_bytes_per_env": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "gr_view_default": (C.c_int, [vp, i32, i32]),
+    # (ctx, env, mode, view, width, height, rgb, gbuf, stream)
+    "gr_view_render": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp]),
     "gr_policy_forward": (C.c_int, [C.POINTER(GrPolicyArgs), vp]),
     "gr_policy_args_size": (C.c_size_t, []),
     "gr_column_sum_partials": (C.c_int, [i64]),

@@ -18,6 +18,7 @@
 #include "gr_camera.h"
 #include "gr_kernels.h"
 #include "gr_math.h"
+#include "gr_viewer.h"
 
 struct gr_ctx {
   gr_config cfg;
@@ -40,6 +41,9 @@ struct gr_ctx {
   gr_cam_const* cam_dev = nullptr;
   gr_camera_buffers cam_buf;
   bool have_cam_buf = false;
+  // the RGB viewer's scratch (gr_view_render): header, gate slots, obstacle slots for the context's maxima
+  float* view_scratch = nullptr;
+  size_t view_scratch_floats = 0;
   // optional kernel timing (gr_set_timing)
   std::vector<hipEvent_t> ev;  // [2 * GR_TIMING_RING]
   int ev_next = 0;
@@ -293,6 +297,7 @@ int gr_destroy(gr_ctx* c) {
   if (c->blk_dev) (void)hipFree(c->blk_dev);
   if (c->status_dev) (void)hipFree(c->status_dev);
   if (c->cam_dev) (void)hipFree(c->cam_dev);
+  if (c->view_scratch) (void)hipFree(c->view_scratch);
   if (c->res.stage) (void)hipFree(c->res.stage);
   if (c->res.live) (void)hipFree(c->res.live);
   delete c;
@@ -879,6 +884,106 @@ int gr_camera_bytes_per_env(const gr_ctx* c, int64_t* render_bytes, int64_t* reu
   *render_bytes = common + img + 2 * 16 + 16;  // depth written; pose planes + istate read
   *reuse_bytes = common + img;                 // depth read
   return GR_OK;
+}
+
+int gr_view_default(float* view, int32_t width, int32_t height) {
+  if (!view || width < GR_VIEW_MIN_SIZE || width > GR_VIEW_MAX_WIDTH || height < GR_VIEW_MIN_SIZE ||
+      height > GR_VIEW_MAX_HEIGHT)
+    return GR_ERR_ARG;
+  for (int i = 0; i < GR_VIEW_FLOATS; ++i) view[i] = 0.0f;
+  // 90 degree vertical field of view, square pixels, principal point at the centre
+  view[GR_VIEW_FX] = view[GR_VIEW_FY] = 0.5f * (float)height;
+  view[GR_VIEW_CX] = 0.5f * (float)width;
+  view[GR_VIEW_CY] = 0.5f * (float)height;
+  view[GR_VIEW_MAX_DISTANCE] = 40.0f;
+  view[GR_VIEW_CHASE_BACK] = 1.5f;
+  view[GR_VIEW_CHASE_UP] = 0.6f;
+  view[GR_VIEW_CHASE_AHEAD] = 1.0f;
+  view[GR_VIEW_EYE] = -3.0f;
+  view[GR_VIEW_EYE + 2] = 2.0f;
+  view[GR_VIEW_TARGET + 2] = 0.5f;
+  return GR_OK;
+}
+
+int gr_view_render(gr_ctx* c, int32_t env, int32_t mode, const float* view, int32_t width, int32_t height,
+                   uint8_t* rgb, float* gbuf, void* stream) {
+  if (!c) return GR_ERR_ARG;
+  if (!view) return fail(c, GR_ERR_ARG, "gr_view_render: view is null");
+  if (env < 0 || env >= c->cfg.num_envs) return fail(c, GR_ERR_ARG, "gr_view_render: env out of range");
+  if (mode != GR_VIEW_FPV && mode != GR_VIEW_CHASE && mode != GR_VIEW_FIXED)
+    return fail(c, GR_ERR_ARG, "gr_view_render: unknown mode");
+  if (width < GR_VIEW_MIN_SIZE || width > GR_VIEW_MAX_WIDTH || height < GR_VIEW_MIN_SIZE || height > GR_VIEW_MAX_HEIGHT)
+    return fail(c, GR_ERR_ARG, "gr_view_render: width in [16, 1920], height in [16, 1080]");
+  if (!rgb && !gbuf) return fail(c, GR_ERR_ARG, "gr_view_render: rgb and gbuf are both null");
+  if ((reinterpret_cast<uintptr_t>(rgb) & 3u) || !aligned16(gbuf))
+    return fail(c, GR_ERR_ARG, "gr_view_render: rgb must be 4-byte aligned, gbuf 16-byte aligned");
+  for (int i = 0; i < GR_VIEW_FLOATS; ++i)
+    if (!std::isfinite(view[i])) return fail(c, GR_ERR_ARG, "gr_view_render: non-finite view entry");
+  if (!(view[GR_VIEW_FX] > 0.0f) || !(view[GR_VIEW_FY] > 0.0f) || !(view[GR_VIEW_MAX_DISTANCE] > 0.0f))
+    return fail(c, GR_ERR_ARG, "gr_view_render: fx, fy and max_distance must be positive");
+  const float* eye = view + GR_VIEW_EYE;
+  const float* tgt = view + GR_VIEW_TARGET;
+  if (mode == GR_VIEW_FIXED && eye[0] == tgt[0] && eye[1] == tgt[1] && eye[2] == tgt[2])
+    return fail(c, GR_ERR_ARG, "gr_view_render: eye and target coincide");
+  if (!c->have_tracks || !c->table) return fail(c, GR_ERR_ARG, "gr_view_render: terrain not loaded");
+  if (!c->have_buf) return fail(c, GR_ERR_ARG, "gr_view_render: state buffers not bound");
+  gr::ViewArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.max_obst = c->obst.records ? c->obst.max_obstacles : 0;
+  if ((size_t)c->cfg.max_gates + (size_t)a.max_obst + 1 > 15000)
+    return fail(c, GR_ERR_ARG, "gr_view_render: more primitives per track than a tile's list holds");
+  const size_t need = gr::view_scratch_floats(c->cfg.max_gates, a.max_obst);
+  if (need > c->view_scratch_floats) {  // (first call, or the obstacle capacity grew: nothing may read the old one)
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && c->view_scratch) e = hipFree(c->view_scratch);
+    c->view_scratch = nullptr;
+    c->view_scratch_floats = 0;
+    if (e == hipSuccess) e = hipMalloc(&c->view_scratch, need * sizeof(float));
+    if (e != hipSuccess) return hip_fail(c, e, "gr_view_render: scratch");
+    c->view_scratch_floats = need;
+  }
+  a.state = c->buf.state;
+  a.istate = c->buf.istate;
+  a.table = c->table;
+  a.obst = c->obst.records;
+  a.obst_counts = c->obst.counts;
+  a.track_stride = c->kc.track_stride;
+  a.num_levels = c->cfg.num_levels;
+  a.max_gates = c->cfg.max_gates;
+  a.num_envs = c->cfg.num_envs;
+  a.env = env;
+  a.mode = mode;
+  a.width = width;
+  a.height = height;
+  a.fx = view[GR_VIEW_FX];
+  a.fy = view[GR_VIEW_FY];
+  a.cx = view[GR_VIEW_CX];
+  a.cy = view[GR_VIEW_CY];
+  a.max_distance = view[GR_VIEW_MAX_DISTANCE];
+  a.back = view[GR_VIEW_CHASE_BACK];
+  a.up = view[GR_VIEW_CHASE_UP];
+  a.ahead = view[GR_VIEW_CHASE_AHEAD];
+  if (mode == GR_VIEW_FIXED) gr_view_lookat64(eye, tgt, a.cam);
+  if (mode == GR_VIEW_FPV) {
+    gr_cam_const* k = new (std::nothrow) gr_cam_const;
+    if (!k) return fail(c, GR_ERR_ARG, "gr_view_render: out of host memory");
+    if (c->cam_enabled) {
+      *k = c->cam_k;
+    } else {
+      gr_camera_config def;
+      gr_camera_config_default(&def);
+      gr_cam_derive(&def, c->cfg.step_dt, k);
+    }
+    for (int i = 0; i < 3; ++i) a.off_p[i] = k->off_p[i];
+    for (int i = 0; i < 9; ++i) a.R_off[i] = k->R_off[i];
+    delete k;
+  }
+  for (int i = 0; i < 3; ++i) a.half[i] = c->cfg.collider_half[i];
+  a.scratch = c->view_scratch;
+  a.gbuf = gbuf;
+  a.rgb = rgb;
+  hipError_t e = gr::launch_view(a, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : hip_fail(c, e, "gr_view_render");
 }
 
 int gr_policy_forward(const gr_policy_args* a, void* stream) {

@@ -20,11 +20,13 @@ import time
 from collections.abc import Mapping
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from .. import _abi
 from .racing_cfg import RacingEnvCfg
 from .tracks import build_tracks
+from .viewer import ViewerCfg, mode_id, view_array
 
 LOG_RING = 64
 # diagnostics (scripts/prof_regen.py): a list to append (label, time.perf_counter()) stamps to inside
@@ -93,11 +95,14 @@ class _EpisodeLog(Mapping):
 class RacingEnv:
     """Vectorised drone-racing env (one shard of envs on one GPU)."""
 
-    metadata = {"render_modes": [None]}
+    metadata = {"render_modes": [None, "rgb_array"]}
 
-    def __init__(self, cfg: RacingEnvCfg, render_mode=None, **kwargs):
+    def __init__(self, cfg: RacingEnvCfg, render_mode=None, viewer=None, **kwargs):
         self.cfg = cfg
         self.render_mode = render_mode
+        # the RGB viewer (render / render_view): its buffers are allocated on the first frame, never without one
+        self.viewer = viewer if viewer is not None else ViewerCfg()
+        self._view_bufs: dict = {}
         self.device = torch.device(cfg.sim.device)
         if self.device.type != "cuda":
             raise RuntimeError(
@@ -793,6 +798,44 @@ class RacingEnv:
     def seed(self, seed: int = -1) -> int:
         return seed
 
+    # ------------------------------------------------------------------ viewer
+    def render_view(self, env_id=None, mode=None, view=None, size=None, gbuffer=False):
+        """One frame of env `env_id` (gr_view_render: a HIP ray cast of its track from the viewer's camera) on the
+        current stream.  mode: "fpv" | "chase" | "fixed"; view: a float32 [GR_VIEW_FLOATS] array (viewer.view_array;
+        default: the env's ViewerCfg at `size`); size: (width, height).  Returns the device tensor rgb uint8
+        [H, W, 3]; with gbuffer=True (rgb, id int32 [H, W], depth float32 [H, W], normal float32 [3, H, W]).  The
+        tensors are reused by the next call with the same size."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("render_view is not meant for a hipGraph capture (it may allocate and synchronise)")
+        vc = self.viewer
+        w, h = (vc.width, vc.height) if size is None else (int(size[0]), int(size[1]))
+        e = vc.env_id if env_id is None else int(env_id)
+        v = view_array(vc, w, h) if view is None else view
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        if v.shape != (_abi.GR_VIEW_FLOATS,):
+            raise ValueError(f"view: a float32 array of {_abi.GR_VIEW_FLOATS} entries")
+        if not (16 <= w <= 1920 and 16 <= h <= 1080):
+            raise ValueError(f"viewer size {w}x{h}: width in [16, 1920], height in [16, 1080]")
+        bufs = self._view_bufs.setdefault((w, h), {})
+        if "rgb" not in bufs:
+            bufs["rgb"] = torch.zeros(h, w, 3, dtype=torch.uint8, device=self.device)
+        if gbuffer and "gbuf" not in bufs:
+            bufs["gbuf"] = torch.zeros(_abi.GR_VIEW_GBUF_WORDS, h, w, dtype=torch.float32, device=self.device)
+        rgb, gb = bufs["rgb"], bufs["gbuf"] if gbuffer else None
+        self._call("gr_view_render", e, mode_id(vc.mode if mode is None else mode), v.ctypes.data, w, h,
+                   rgb.data_ptr(), gb.data_ptr() if gb is not None else None, _abi.raw_stream(self.device))
+        if not gbuffer:
+            return rgb
+        return (rgb, gb[_abi.GR_VIEW_G_ID].view(torch.int32), gb[_abi.GR_VIEW_G_DEPTH],
+                gb[_abi.GR_VIEW_G_NORMAL:_abi.GR_VIEW_G_NORMAL + 3])
+
+    def render(self):
+        """gym's render(): None without a render mode; with render_mode="rgb_array" the viewer's frame of the
+        current state as a numpy uint8 [H, W, 3] array (synchronises: a device-to-host copy)."""
+        if self.render_mode != "rgb_array":
+            return None
+        return self.render_view().cpu().numpy()
+
     def close(self):
         if getattr(self, "_builder", None) is not None:
             # (a running build stages into the context's arrays: wait for it before the context goes)
@@ -829,7 +872,7 @@ class RslRlVecEnvWrapper:
 
     @property
     def unwrapped(self) -> RacingEnv:
-        return self.env
+        return self.env.unwrapped  # (through a RecordVideo in between, if any)
 
     @property
     def render_mode(self):
@@ -845,6 +888,10 @@ class RslRlVecEnvWrapper:
 
     def seed(self, seed: int = -1) -> int:
         return self.env.seed(seed)
+
+    def render(self):
+        """RacingEnv.render (through a RecordVideo in between, if any)."""
+        return self.env.render()
 
     def check_device_status(self):
         """RacingEnv.check_device_status."""

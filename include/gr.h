@@ -42,8 +42,9 @@ extern "C" {
  * 8: gr_offline_collect / gr_offline_pgd_step.  9: gr_stem_image / gr_bn_act in place of the stem entry points' and the
  * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit).  10: gr_mlp_net.h1mask
  * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired).  11: gr_gru_step, gr_gru_seq_forward,
- * gr_gru_seq_backward, gr_gru_scratch_floats.  12: the gr_gru_wide_* family (d <= 256, the input gradient) */
-#define GR_ABI_VERSION 12
+ * gr_gru_seq_backward, gr_gru_scratch_floats.  12: the gr_gru_wide_* family (d <= 256, the input gradient).
+ * 13: gr_view_default, gr_view_render (the RGB viewer) */
+#define GR_ABI_VERSION 13
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -373,6 +374,57 @@ int gr_bind_camera_buffers(gr_ctx* ctx, const gr_camera_buffers* bufs);
 int gr_camera_render(gr_ctx* ctx, int mode, const uint8_t* mask, void* stream);
 /* algorithmic HBM bytes per env of one render call, with and without the re-render */
 int gr_camera_bytes_per_env(const gr_ctx* ctx, int64_t* render_bytes, int64_t* reuse_bytes);
+
+/* RGB viewer (ABI 13; gr_viewer.hip, gr_viewer.h): one frame of one env's track (its gates, obstacles, the ground
+ * plane and, in the third-person modes, the drone as a box with the collider's half extents) from a pinhole camera
+ * of any resolution, ray-cast with the depth camera's own hit functions.  What the reference gets from
+ * gym.make(render_mode="rgb_array") under gym.wrappers.RecordVideo (standalone/rsl_rl/train.py:102-113).
+ *   mode   GR_VIEW_FPV: the env's depth-sensor pose (the enabled camera's offset, else gr_camera_config_default's; no
+ *          drone).  GR_VIEW_CHASE: behind and above the drone along its heading (the body x axis on the horizontal;
+ *          the world x axis when that projection is shorter than 1e-3), looking at a point ahead of it.
+ *          GR_VIEW_FIXED: eye and target in the env-local frame, z up.
+ *   view   HOST array of GR_VIEW_FLOATS floats (gr_view_default fills it for a width x height image: 90 degree
+ *          vertical field of view, square pixels, centred, max_distance 40, chase 1.5 m back / 0.6 m up / 1 m ahead,
+ *          eye (-3, 0, 2), target (0, 0, 0.5)).
+ *   rgb    device uint8 [height][width][3] (4-byte aligned), or NULL.
+ *   gbuf   device [GR_VIEW_GBUF_WORDS][height][width] 4-byte words (16-byte aligned), or NULL: plane GR_VIEW_G_ID int32
+ *          (GR_VIEW_ID_MISS, GR_VIEW_ID_GROUND, 1 + g for gate g, 1 + G + k for obstacle k of a track of G gates,
+ *          GR_VIEW_ID_DRONE), plane GR_VIEW_G_DEPTH the distance to the image plane clipped at max_distance, planes
+ *          GR_VIEW_G_NORMAL .. + 2 the unit surface normal in the env-local frame (zero for a miss).  With
+ *          GR_VIEW_FPV, the sensor's intrinsics, size and max_distance the depth plane is the depth camera's, bit
+ *          for bit.
+ * GR_ERR_ARG before any launch: env out of range, unknown mode, width outside [16, 1920] or height outside
+ * [16, 1080], both outputs NULL, a misaligned pointer, non-finite or non-positive fx / fy / max_distance, non-finite
+ * cx / cy / chase / eye / target, eye == target (GR_VIEW_FIXED), tracks or state buffers not bound.  Reads the
+ * context's current terrain arrays and the bound state planes on `stream`, writes only rgb, gbuf and a scratch the
+ * context owns (allocated at the first call: that call synchronises).  Not for a hipGraph capture. */
+#define GR_VIEW_FPV 0
+#define GR_VIEW_CHASE 1
+#define GR_VIEW_FIXED 2
+#define GR_VIEW_FLOATS 16
+#define GR_VIEW_FX 0
+#define GR_VIEW_FY 1
+#define GR_VIEW_CX 2
+#define GR_VIEW_CY 3
+#define GR_VIEW_MAX_DISTANCE 4
+#define GR_VIEW_CHASE_BACK 5
+#define GR_VIEW_CHASE_UP 6
+#define GR_VIEW_CHASE_AHEAD 7
+#define GR_VIEW_EYE 8     /* 3 floats */
+#define GR_VIEW_TARGET 11 /* 3 floats; 14-15 spare (zero) */
+#define GR_VIEW_GBUF_WORDS 5
+#define GR_VIEW_G_ID 0
+#define GR_VIEW_G_DEPTH 1
+#define GR_VIEW_G_NORMAL 2
+#define GR_VIEW_ID_MISS -1
+#define GR_VIEW_ID_GROUND 0
+#define GR_VIEW_ID_DRONE 1000000
+#define GR_VIEW_MIN_SIZE 16
+#define GR_VIEW_MAX_WIDTH 1920
+#define GR_VIEW_MAX_HEIGHT 1080
+int gr_view_default(float* view, int32_t width, int32_t height);
+int gr_view_render(gr_ctx* ctx, int32_t env, int32_t mode, const float* view, int32_t width, int32_t height,
+                   uint8_t* rgb, float* gbuf, void* stream);
 
 /*
  * Rollout inference of the rsl_rl ActorCritic (PPO.act: standalone/rsl_rl/ext/algorithms/ppo.py:71-85

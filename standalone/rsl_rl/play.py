@@ -4,7 +4,9 @@ Same flow as the reference: resolve the checkpoint from logs/rsl_rl/<experiment>
 build the env and the runner, load, export the policy next to the checkpoint (exported/), then step
 the env with the inference policy.  There is no simulator window: the loop runs --max_steps steps
 (the reference runs until the app closes) and prints a JSON summary; --show_camera writes env 0's
-depth image as PGM frames instead of an OpenCV window.
+depth image as PGM frames instead of an OpenCV window; --video records the first --video_length steps from the
+HIP viewer's chase camera as `<checkpoint dir>/videos/play/rl-video-step-0.gif` (reference play.py: RecordVideo with
+a trigger at step 0).
 
     python standalone/rsl_rl/play.py --task DiffLab-Quadcopter-CTBR-Racing-v0 --num_envs 64
 """
@@ -25,8 +27,10 @@ from train import get_checkpoint_path  # noqa: E402
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Play an RL agent with RSL-RL.")
-    p.add_argument("--video", action="store_true", default=False, help="(unsupported: no renderer)")
-    p.add_argument("--video_length", type=int, default=200)
+    p.add_argument("--video", action="store_true", default=False, help="Record a video of the first steps.")
+    p.add_argument("--video_length", type=int, default=200, help="Length of the recorded video (in steps).")
+    p.add_argument("--video_env", type=int, default=0, help="Index of the env the viewer follows.")
+    p.add_argument("--video_size", type=str, default="640x480", help="Frame size of the video, WxH.")
     p.add_argument("--disable_fabric", action="store_true", default=False, help="(ignored)")
     p.add_argument("--num_envs", type=int, default=None)
     p.add_argument("--task", type=str, default=None)
@@ -53,8 +57,6 @@ def _write_pgm(path, img):
 
 def main(argv=None):
     args, _ = build_parser().parse_known_args(argv)
-    if args.video:
-        raise SystemExit("--video is not supported: this build has no renderer")
     import importlib
 
     import torch
@@ -77,7 +79,19 @@ def main(argv=None):
     print(f"[INFO] Loading experiment from directory: {log_root_path}")
     resume_path = get_checkpoint_path(log_root_path, agent_cfg.load_run, agent_cfg.load_checkpoint)
 
-    env = RslRlVecEnvWrapper(registry.make(task, cfg=env_cfg))
+    if args.video:
+        from generalizableracing_amd.envs.record_video import RecordVideo
+        from generalizableracing_amd.envs.viewer import ViewerCfg, parse_size
+
+        vw, vh = parse_size(args.video_size)
+        env = registry.make(task, cfg=env_cfg, render_mode="rgb_array",
+                            viewer=ViewerCfg(width=vw, height=vh, env_id=args.video_env))
+        print("[INFO] Recording videos during play.")
+        env = RecordVideo(env, video_folder=os.path.join(os.path.dirname(resume_path), "videos", "play"),
+                          step_trigger=lambda step: step == 0, video_length=args.video_length)
+    else:
+        env = registry.make(task, cfg=env_cfg)
+    env = RslRlVecEnvWrapper(env)
     print(f"[INFO]: Loading model checkpoint from: {resume_path}")
     runner = OnPolicyRunner(env, agent_cfg.to_dict(), log_dir=None, device=device)
     runner.load(resume_path)

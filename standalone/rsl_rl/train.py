@@ -13,7 +13,10 @@ Multi-GPU (one env shard per GPU, PPO gradients all-reduced over RCCL):
         standalone/rsl_rl/train.py --task DiffLab-Quadcopter-CTBR-Racing-State-v0 --num_envs 65536
 
 There is no simulator app to launch: `--headless` and the other AppLauncher
-flags are accepted and ignored; `--video` is rejected (no renderer).
+flags are accepted and ignored.  `--video` records as the reference does (train.py:102-113): the env is made with
+render_mode="rgb_array" and wrapped in RecordVideo, which writes `<log_dir>/videos/train/rl-video-step-<k>.gif`
+(`--video_length` frames every `--video_interval` steps) from the HIP viewer's chase camera on env `--video_env`
+at `--video_size`.  Without `--video` no frame is rendered and nothing is allocated for one.
 """
 from __future__ import annotations
 
@@ -32,9 +35,11 @@ import cli_args  # noqa: E402  isort: skip
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Train an RL agent with RSL-RL.")
-    p.add_argument("--video", action="store_true", default=False, help="(unsupported: no renderer)")
-    p.add_argument("--video_length", type=int, default=200)
-    p.add_argument("--video_interval", type=int, default=2000)
+    p.add_argument("--video", action="store_true", default=False, help="Record videos during training.")
+    p.add_argument("--video_length", type=int, default=200, help="Length of the recorded video (in steps).")
+    p.add_argument("--video_interval", type=int, default=2000, help="Interval between video recordings (in steps).")
+    p.add_argument("--video_env", type=int, default=0, help="Index of the env the viewer follows.")
+    p.add_argument("--video_size", type=str, default="640x480", help="Frame size of the video, WxH.")
     p.add_argument("--num_envs", type=int, default=None, help="Number of environments per GPU.")
     p.add_argument("--task", type=str, default=None, help="Name of the task.")
     p.add_argument("--seed", type=int, default=42, help="Seed used for the environment")
@@ -80,8 +85,6 @@ def get_checkpoint_path(log_path: str, run_dir: str = ".*", checkpoint: str = ".
 
 def main(argv=None):
     args, _unknown = build_parser().parse_known_args(argv)
-    if args.video:
-        raise SystemExit("--video is not supported: this build has no renderer")
     import torch
     import yaml
 
@@ -128,7 +131,20 @@ def main(argv=None):
     if args.deterministic:
         torch.use_deterministic_algorithms(True)
 
-    env = RslRlVecEnvWrapper(registry.make(task, cfg=env_cfg))
+    if args.video:
+        from generalizableracing_amd.envs.record_video import RecordVideo
+        from generalizableracing_amd.envs.viewer import ViewerCfg, parse_size
+
+        vw, vh = parse_size(args.video_size)
+        env = registry.make(task, cfg=env_cfg, render_mode="rgb_array",
+                            viewer=ViewerCfg(width=vw, height=vh, env_id=args.video_env))
+        print("[INFO] Recording videos during training.")
+        env = RecordVideo(env, video_folder=os.path.join(log_dir, "videos", "train"),
+                          step_trigger=lambda step: step % args.video_interval == 0, video_length=args.video_length,
+                          rank=rank)
+    else:
+        env = registry.make(task, cfg=env_cfg)
+    env = RslRlVecEnvWrapper(env)
     runner = OnPolicyRunner(env, agent_cfg.to_dict(), log_dir=log_dir if rank == 0 else None, device=device)
     if agent_cfg.resume:
         resume_path = get_checkpoint_path(log_root_path, agent_cfg.load_run, agent_cfg.load_checkpoint)
