@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgr.so")
 
 # ---- constants (include/gr.h) ----
-GR_ABI_VERSION = 13
+GR_ABI_VERSION = 14
 GR_INTEGRATOR_DD_EXPLICIT = 0
 GR_INTEGRATOR_SEMI_IMPLICIT = 1
 
@@ -279,6 +279,10 @@ GR_VIEW_CHASE_BACK, GR_VIEW_CHASE_UP, GR_VIEW_CHASE_AHEAD, GR_VIEW_EYE, GR_VIEW_
 GR_VIEW_GBUF_WORDS = 5
 GR_VIEW_G_ID, GR_VIEW_G_DEPTH, GR_VIEW_G_NORMAL = 0, 1, 2
 GR_VIEW_ID_MISS, GR_VIEW_ID_GROUND, GR_VIEW_ID_DRONE = -1, 0, 1000000
+# tape planes of the differentiable step (gr_diff_record / gr_diff_loss / gr_diff_backward)
+GR_DIFF_PLANES = 18
+(DT_POSQ, DT_QV, DT_VW, DT_WA, DT_CTRL, DT_U, DT_RST0, DT_RST1, DT_PAR0, DT_PAR1, DT_PAR2, DT_PAR3, DT_TT, DT_XP0, DT_XP1,
+ DT_XP2, DT_XP3, DT_GOAL) = range(18)
 GR_STEP_L2, GR_STEP_LDS, GR_STEP_LDS8, GR_STEP_LDS8_LEAN, GR_STEP_OBST, GR_STEP_OBST_LEAN = range(6)
 STEP_KERNEL_NAMES = ["step_kernel<false, false>", "step_kernel<true, false>", "step_kernel<true, false, 8>",
                      "step_kernel<true, false, 8, 1>", "step_kernel<false, true>", "step_kernel<false, true, 0, 1>"]
@@ -336,6 +340,13 @@ SIGNATURES = {
     "gr_view_default": (C.c_int, [vp, i32, i32]),
     # (ctx, env, mode, view, width, height, rgb, gbuf, stream)
     "gr_view_render": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    # BPTT through the analytic step: (ctx, weights[3], gamma); (ctx); (ctx, actions, tape_row, stream);
+    # (ctx, gates, tape_row, loss, loss_terms, stream); (ctx, tape, steps, scale, grad_actions, stream)
+    "gr_diff_config": (C.c_int, [vp, vp, f32]),
+    "gr_diff_row_floats": (i64, [vp]),
+    "gr_diff_record": (C.c_int, [vp, vp, vp, vp]),
+    "gr_diff_loss": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "gr_diff_backward": (C.c_int, [vp, vp, i32, f32, vp, vp]),
     "gr_policy_forward": (C.c_int, [C.POINTER(GrPolicyArgs), vp]),
     "gr_policy_args_size": (C.c_size_t, []),
     "gr_column_sum_partials": (C.c_int, [i64]),

@@ -16,6 +16,7 @@
 
 #include "../../include/gr.h"
 #include "gr_camera.h"
+#include "gr_diff.h"
 #include "gr_kernels.h"
 #include "gr_math.h"
 #include "gr_viewer.h"
@@ -63,6 +64,8 @@ struct gr_ctx {
     int32_t hdr_host[4] = {0, 0, 0, 0};
   } res;
   std::mutex err_mu;  // gr_terrain_stage may fail on another host thread
+  float diff_w[3] = {1.0f, 0.05f, 0.5f};  // gr_diff_config: LossesCfg's weights (racing_ctbr_env.py:330-353)
+  float diff_gamma = 0.92f;               // grad_decay_factor
   int64_t terrain_epoch = 0;  // gr_terrain_reserve calls: each one moves the terrain arrays a graph may have baked in
 };
 
@@ -1587,6 +1590,83 @@ int gr_adaptive_lr(const float* kl, float* lr, double desired_kl, double lr_min,
   const hipError_t e = gr::launch_adaptive_lr(kl, lr, (float)(desired_kl * 2.0), (float)(desired_kl / 2.0),
                                               (float)lr_min, (float)lr_max, (hipStream_t)stream);
   return e == hipSuccess ? GR_OK : GR_ERR_HIP;
+}
+
+// ---- BPTT through the analytic step (gr_diff.hip)
+static int diff_ready(gr_ctx* c, const char* who, gr_diff_consts* k) {
+  if (!c) return GR_ERR_ARG;
+  const gr_config& g = c->cfg;
+  if (g.integrator != GR_INTEGRATOR_DD_EXPLICIT || g.use_motor_model || g.dr_rotor)
+    return fail(c, GR_ERR_ARG, std::string(who) + ": the context's configuration is not lean (the differentiable step "
+                "needs integrator GR_INTEGRATOR_DD_EXPLICIT, use_motor_model 0 and dr_rotor 0)");
+  if (g.action_lag != 0 && g.action_lag != 1) return fail(c, GR_ERR_ARG, std::string(who) + ": action_lag must be 0 or 1");
+  std::memset(k, 0, sizeof(*k));
+  k->num_envs = g.num_envs;
+  k->lag = g.action_lag;
+  k->dr_plant = g.dr_plant;
+  k->num_levels = g.num_levels;
+  k->max_gates = g.max_gates;
+  k->num_types = g.num_types;
+  k->dt = g.step_dt;
+  k->gravity = g.gravity;
+  k->thrust_ratio = g.max_thrust_weight_ratio;
+  k->rate_bound = g.body_rate_bound;
+  k->thrust_lo = c->kc.thrust_lo;
+  k->thrust_hi = c->kc.thrust_hi;
+  k->gamma = c->diff_gamma;
+  for (int i = 0; i < 3; ++i) k->inertia[i] = g.inertia[i];
+  k->w_target = c->diff_w[0];
+  k->w_vel = c->diff_w[1];
+  k->w_fall = c->diff_w[2];
+  return GR_OK;
+}
+
+int gr_diff_config(gr_ctx* c, const float* weights, float gamma) {
+  if (!c) return GR_ERR_ARG;
+  if (!weights) return fail(c, GR_ERR_ARG, "gr_diff_config: weights is null");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(weights[i])) return fail(c, GR_ERR_ARG, "gr_diff_config: non-finite loss weight");
+  if (!std::isfinite(gamma)) return fail(c, GR_ERR_ARG, "gr_diff_config: non-finite gamma");
+  for (int i = 0; i < 3; ++i) c->diff_w[i] = weights[i];
+  c->diff_gamma = gamma;
+  return GR_OK;
+}
+
+int64_t gr_diff_row_floats(const gr_ctx* c) { return c ? (int64_t)GR_DIFF_PLANES * c->cfg.num_envs * 4 : GR_ERR_ARG; }
+
+int gr_diff_record(gr_ctx* c, const float* actions, float* tape_row, void* stream) {
+  gr_diff_consts k;
+  if (int r = diff_ready(c, "gr_diff_record", &k)) return r;
+  if (!tape_row || !aligned16(tape_row)) return fail(c, GR_ERR_ARG, "gr_diff_record: tape_row must be a 16-byte aligned device buffer");
+  if (!k.lag && (!actions || !aligned16(actions)))
+    return fail(c, GR_ERR_ARG, "gr_diff_record: actions must be a 16-byte aligned [N][4] fp32 buffer");
+  if (!c->have_buf) return fail(c, GR_ERR_ARG, "gr_diff_record: state buffers not bound");
+  hipError_t e = gr::launch_diff_record(k, c->buf.state, actions, tape_row, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : hip_fail(c, e, "gr_diff_record");
+}
+
+int gr_diff_loss(gr_ctx* c, const float* gates, float* tape_row, float* loss, float* loss_terms, void* stream) {
+  gr_diff_consts k;
+  if (int r = diff_ready(c, "gr_diff_loss", &k)) return r;
+  if (!gates || !loss || !loss_terms) return fail(c, GR_ERR_ARG, "gr_diff_loss: null pointer");
+  if (!tape_row || !aligned16(tape_row)) return fail(c, GR_ERR_ARG, "gr_diff_loss: tape_row must be a 16-byte aligned device buffer");
+  if (!c->have_buf) return fail(c, GR_ERR_ARG, "gr_diff_loss: state buffers not bound");
+  hipError_t e = gr::launch_diff_loss(k, c->buf.istate, c->buf.dones, gates, tape_row, loss, loss_terms,
+                                      (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : hip_fail(c, e, "gr_diff_loss");
+}
+
+int gr_diff_backward(gr_ctx* c, const float* tape, int32_t steps, float scale, float* grad_actions, void* stream) {
+  gr_diff_consts k;
+  if (int r = diff_ready(c, "gr_diff_backward", &k)) return r;
+  if (steps < 1) return fail(c, GR_ERR_ARG, "gr_diff_backward: steps must be at least 1");
+  if ((int64_t)steps * GR_DIFF_PLANES * (int64_t)k.num_envs >= (int64_t)1 << 31)
+    return fail(c, GR_ERR_ARG, "gr_diff_backward: steps * GR_DIFF_PLANES * num_envs exceeds the kernel's 32-bit offsets");
+  if (!std::isfinite(scale)) return fail(c, GR_ERR_ARG, "gr_diff_backward: non-finite scale");
+  if (!tape || !aligned16(tape) || !grad_actions || !aligned16(grad_actions))
+    return fail(c, GR_ERR_ARG, "gr_diff_backward: tape and grad_actions must be 16-byte aligned device buffers");
+  hipError_t e = gr::launch_diff_backward(k, tape, steps, scale, grad_actions, (hipStream_t)stream);
+  return e == hipSuccess ? GR_OK : hip_fail(c, e, "gr_diff_backward");
 }
 
 int gr_test_dynamics(gr_ctx* c, int n, int mode, const float* si, const float* ab, const float* cmd, const float* ci,

@@ -16,6 +16,7 @@
 #define GR_STAMP_SLOTS 16
 
 struct gr_cam_const;  // gr_camera.h
+struct gr_diff_consts;  // gr_diff.h
 
 namespace gr {
 
@@ -277,6 +278,14 @@ inline CamLaunch camera_launch_config(int width, int height, int max_gates, bool
   const int slots = obst ? (slots_req > 0 ? slots_req : GR_CAM_OBST_SLOTS) : 0;
   return {CAM_WAVES, slots, camera_lds_bytes(width, height, max_gates, CAM_WAVES, slots)};
 }
+
+// gr_diff.hip: BPTT through the analytic step (tape record, losses, the window's adjoint)
+hipError_t launch_diff_record(const ::gr_diff_consts& k, const float* state, const float* actions, float* row,
+                              hipStream_t s);
+hipError_t launch_diff_loss(const ::gr_diff_consts& k, const int32_t* istate, const int64_t* dones, const float* gates,
+                            float* row, float* loss, float* terms, hipStream_t s);
+hipError_t launch_diff_backward(const ::gr_diff_consts& k, const float* tape, int T, float scale, float* grad,
+                                hipStream_t s);
 
 // which step_kernel instantiation gr_step launches for these arguments (GR_STEP_* of gr.h)
 int step_variant(const KArgs& a);

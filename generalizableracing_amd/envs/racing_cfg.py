@@ -90,6 +90,19 @@ class CameraCfg:
 
 
 @dataclass
+class LossesCfg:
+    """The differentiable losses of the racing task (LossesCfg, racing_ctbr_env.py:330-353; mdp/losses.py:72-117):
+    the weight of each term, 0 disables it."""
+
+    racing_target: float = 1.0    # distance to the current gate's ground-truth centre
+    racing_vel: float = 0.05      # mean squared world velocity
+    racing_falling: float = 0.5   # 1 / (1 + z + 10 z^2)
+
+    def weights(self) -> tuple:
+        return (float(self.racing_target), float(self.racing_vel), float(self.racing_falling))
+
+
+@dataclass
 class RacingEnvCfg:
     scene: SceneCfg = field(default_factory=SceneCfg)
     terrain: TerrainCfg = field(default_factory=TerrainCfg)
@@ -104,6 +117,14 @@ class RacingEnvCfg:
     # front depth camera: None = the state-only task (obs 16); CameraCfg() = the reference's
     # vision task (obs 16 + 96*72, racing_ctbr_env.py:141-160)
     camera: CameraCfg | None = None
+    # the diff_rl workflow (ManagerBasedDiffRLEnv with is_differentiable_physics, manager_based_diff_rl_env.py:205-257):
+    # step also records a tape row and the differentiable losses; loss_action_grad() returns the window's gradient.
+    # Off: nothing is allocated or launched
+    is_differentiable_physics: bool = False
+    losses: LossesCfg = field(default_factory=LossesCfg)
+    grad_decay_factor: float = 0.92         # DroneDynamics.align (dynamics.yaml)
+    diff_window: int = 48                   # steps the tape holds between two detach() calls (not in the reference)
+    diff_fused: bool = True                 # the HIP record / loss / adjoint kernels; False: the torch path (not in the reference)
     # shard description for multi-GPU runs (env ids offset for the RNG, track seed offset)
     env_id_offset: int = 0
     track_seed_offset: int = 0

@@ -92,6 +92,29 @@ class _EpisodeLog(Mapping):
         return len(self._keys)
 
 
+class _LossLog(Mapping):
+    """extras["log_losses"] of one step: name -> mean of the weighted loss term over the envs, formed when read (no
+    launch and no host sync in step)."""
+
+    __slots__ = ("_terms",)
+
+    def __init__(self, terms: torch.Tensor):
+        self._terms = terms
+
+    def __getitem__(self, k):
+        from ..diff_rl.diff_ops import LOSS_TERMS
+
+        return self._terms[:, LOSS_TERMS.index(k)].mean()
+
+    def __iter__(self):
+        from ..diff_rl.diff_ops import LOSS_TERMS
+
+        return iter(LOSS_TERMS)
+
+    def __len__(self):
+        return 3
+
+
 class RacingEnv:
     """Vectorised drone-racing env (one shard of envs on one GPU)."""
 
@@ -184,6 +207,20 @@ class RacingEnv:
                 cb.obs_critic = self._img_sets[k]["critic"].data_ptr()
                 self._cam_bufs.append(cb)
         self.extras: dict = {}
+        # ---- the diff_rl workflow's tape (cfg.is_differentiable_physics): allocated only with the flag on
+        self._diff = None
+        if cfg.is_differentiable_physics:
+            from ..diff_rl.diff_ops import DiffTape
+
+            if self._regen_steps is not None:
+                # the terrain interval step resets every env inside `step` and moves the gate table: the tape's done
+                # flags, its goals and the step's extras are not carried through it
+                raise ValueError("is_differentiable_physics is not built for periodic terrain regeneration: set "
+                                 "cfg.terrain.regen_interval_s = None")
+            self._diff = DiffTape(ctx, self._gcfg, cfg.diff_window, dev, fused=cfg.diff_fused,
+                                  weights=cfg.losses.weights(), gamma=cfg.grad_decay_factor)
+            self._diff_gates = self.track_gates  # the device table gr_bind_tracks holds (no regeneration: it stays)
+            self._diff_zero = torch.zeros(n, dtype=torch.float32, device=dev)
         self._sink = None  # (policy, critic) tensors of the bound observation sink
         # fp32 sink = the calls' observation OUTPUT (set_obs_sink): the rows are written once, into the storage slot
         self._sink_out = None
@@ -664,11 +701,22 @@ class RacingEnv:
         a = action
         if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous() or a.data_ptr() % 16:
             a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        diff = self._diff
+        if diff is not None:
+            diff.check_room()  # (before any launch)
+            diff.record(self.state, a)
         out, log = self._advance()
         self._call("gr_step", a.data_ptr(), _abi.raw_stream(self.device))
         self._render(_abi.GR_CAM_STEP)
         self.common_step_counter += 1
         self.extras = {"log": log}
+        if diff is not None:
+            # the losses on the step's post-step, pre-reset state against the gate after its reset and command update
+            # (manager_based_diff_rl_env.py:205-257); values only: the gradient is loss_action_grad()
+            losses, terms = diff.loss(self._diff_gates, self.istate[:, _abi.I_PACKED], out["dones"])
+            self.extras["losses"] = losses
+            self.extras["losses_detached"] = self._diff_zero
+            self.extras["log_losses"] = _LossLog(terms)
         if self._regen_steps is not None:
             phase = self.common_step_counter % self._regen_steps
             if phase == 0:
@@ -797,6 +845,27 @@ class RacingEnv:
 
     def seed(self, seed: int = -1) -> int:
         return seed
+
+    # ------------------------------------------------------------------ diff_rl
+    def detach(self):
+        """ManagerBasedDiffRLEnv.detach (the head of every BPTT iteration): the window starts at the next step."""
+        if self._diff is None:
+            raise RuntimeError("detach() needs cfg.is_differentiable_physics")
+        self._diff.rewind()
+
+    def loss_action_grad(self, scale: float | None = None) -> torch.Tensor:
+        """d(scale * sum of the losses since detach())/d(raw action) [T, N, 4] (scale None: 1 / (T * N), the mean of
+        algorithms/bptt.py:38-45): one reverse-time launch over the tape (gr_diff_backward).  With action_lag 1 step
+        t's gradient lands on the action of step t - 1; the window's last action gets zero."""
+        if self._diff is None:
+            raise RuntimeError("loss_action_grad() needs cfg.is_differentiable_physics")
+        T = self._diff.cursor
+        return self._diff.backward(1.0 / (max(T, 1) * self.num_envs) if scale is None else float(scale))
+
+    @property
+    def diff_steps(self) -> int:
+        """Steps recorded since detach()."""
+        return 0 if self._diff is None else self._diff.cursor
 
     # ------------------------------------------------------------------ viewer
     def render_view(self, env_id=None, mode=None, view=None, size=None, gbuffer=False):

@@ -73,4 +73,7 @@ register(
     rsl_rl_l2c2_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterL2C2PPORunnerCfg",
     rsl_rl_lcp_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterLCPPPORunnerCfg",
     rsl_rl_recurrent_cfg_entry_point="generalizableracing_amd.rsl_rl.config:QuadcopterRecurrentPPORunnerCfg",
+    # BPTT through the analytic step (quadcopter_diff/__init__.py:60 registers the key on the racing id; its recipe
+    # there is the vision one, which is not built: this is the MLP recipe of diff_rl_naive_cfg.py:9-32)
+    diff_rl_cfg_entry_point="generalizableracing_amd.diff_rl.config:QuadcopterDiffRLRunnerCfg",
 )

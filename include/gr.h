@@ -43,8 +43,9 @@ extern "C" {
  * *_bnact GEMMs' positional lists; gr_swap_terrain removed (gr_terrain_reserve / _stage / _commit).  10: gr_mlp_net.h1mask
  * and gr_mlp_h1mask_words removed (the h1 sign-bit backward is retired).  11: gr_gru_step, gr_gru_seq_forward,
  * gr_gru_seq_backward, gr_gru_scratch_floats.  12: the gr_gru_wide_* family (d <= 256, the input gradient).
- * 13: gr_view_default, gr_view_render (the RGB viewer) */
-#define GR_ABI_VERSION 13
+ * 13: gr_view_default, gr_view_render (the RGB viewer).  14: gr_diff_config, gr_diff_row_floats, gr_diff_record,
+ * gr_diff_loss, gr_diff_backward (BPTT through the analytic step) */
+#define GR_ABI_VERSION 14
 
 /* ---- status codes ---- */
 #define GR_OK 0
@@ -996,6 +997,70 @@ int gr_test_philox(gr_ctx* ctx, int n, uint32_t c0, uint32_t c1, uint32_t c2, ui
 int gr_debug_read_stamps(uint64_t* host, int n);
 /* The same for the fused policy kernel (16 u64 per wave, gr_policy.hip). */
 int gr_debug_read_policy_stamps(uint64_t* host, int n);
+
+/*
+ * BPTT through the analytic step (ABI 14; gr_diff.hip, gr_diff.h): the reference's second training workflow,
+ * standalone/diff_rl (algorithms/bptt.py:38-45; the losses of ManagerBasedDiffRLEnv.step, manager_based_diff_rl_env.py:
+ * 205-257; DroneDynamics.step / align, .../quadcopter_diff/mdp/dynamics/droneDynamics.py:119-135, 156-180;
+ * CTBRController.compute, controller_diff.py:120-138).  The context's default plant (GR_INTEGRATOR_DD_EXPLICIT, no motor
+ * model, no dr_rotor: "lean") is DroneDynamics.step at the policy dt, so its analytic gradient is the plant's own.
+ * Per step: gr_diff_record before gr_step and gr_diff_loss after it, both read-only on the context's buffers, write
+ * one tape row; per window one gr_diff_backward.  gr_step itself is untouched.
+ *
+ * Tape: rows of GR_DIFF_PLANES float4 planes, each [num_envs] (gr_diff_row_floats floats per row, rows contiguous for
+ * gr_diff_backward; 16-byte aligned).  Planes GR_DT_POSQ .. GR_DT_CTRL, GR_DT_RST0 .. GR_DT_PAR3 are the pre-step
+ * copies of the state planes of the same name (the linearisation point, the drag, gains, filter coefficients, masses
+ * and inertia), and
+ *   GR_DT_U    the squashed action the step applies: tanh(a_t), or with action_lag the lag plane tanh(a_{t-1})
+ *   GR_DT_TT   T+, tau+ (the filtered thrust and torque)
+ *   GR_DT_XP0  p+ xyz, q+ w      GR_DT_XP1  q+ xyz, v+ x      GR_DT_XP2  v+ yz, w_b+ xy      GR_DT_XP3  w_b+ z, 0, 0, 0
+ *   GR_DT_GOAL (gr_diff_loss) the ground-truth centre of the env's gate after the step's reset and command update,
+ *              and 1.0 if the step reset the env (dones), else 0.0
+ *
+ *   gr_diff_config    loss weights (target distance, mean squared velocity, falling; LossesCfg 1.0, 0.05, 0.5; 0
+ *                     disables a term) and the alignment's grad_decay_factor (0.92).  These are the defaults.
+ *   gr_diff_record    actions [num_envs][4] fp32 pre-tanh (read without action_lag only; may be NULL with it).
+ *                     For every env that the step does not reset, the row's x+ and (T+, tau+) equal the planes
+ *                     gr_step writes, bit for bit.
+ *   gr_diff_loss      gates: the DEVICE table [num_types*num_levels][max_gates][GR_GATE_FLOATS] of gr_bind_tracks
+ *                     (the caller guarantees its extent; the kernel clamps type, level and gate id into it).  Reads
+ *                     the bound istate and dones as gr_step left them.  loss [num_envs], loss_terms [num_envs][3]
+ *                     (the weighted terms; loss is their sum), evaluated on the row's x+ (post-step, pre-reset).
+ *   gr_diff_backward  tape: `steps` contiguous rows.  grad_actions [steps][num_envs][4] = scale * d(sum of the
+ *                     window's losses)/d(raw action), one lane per env walking t = steps-1 .. 0 with the adjoints of
+ *                     p, q, v, w_b, T, tau in registers: the adjoint of x+_t is gamma * (the loss's gradient at t +
+ *                     what comes back from t + 1), the filter adjoints are not decayed, both are cut where the row's
+ *                     done flag is set; w_b and alpha_b enter the controller detached; a clamp passes the gradient
+ *                     on its closed interval.  With action_lag step t's gradient lands on row t - 1 (step 0's is
+ *                     dropped, row steps - 1 is zero).  Deterministic.
+ * GR_ERR_ARG before any launch (and before any device use): a context that is not lean, null / misaligned pointers,
+ * steps < 1, steps * GR_DIFF_PLANES * num_envs >= 2^31 (the kernels use 32-bit float4 offsets), non-finite weights.
+ * No allocation, no synchronisation: graph-capturable.
+ */
+#define GR_DIFF_PLANES 18
+#define GR_DT_POSQ 0
+#define GR_DT_QV 1
+#define GR_DT_VW 2
+#define GR_DT_WA 3
+#define GR_DT_CTRL 4
+#define GR_DT_U 5
+#define GR_DT_RST0 6
+#define GR_DT_RST1 7
+#define GR_DT_PAR0 8
+#define GR_DT_PAR1 9
+#define GR_DT_PAR2 10
+#define GR_DT_PAR3 11
+#define GR_DT_TT 12
+#define GR_DT_XP0 13
+#define GR_DT_XP1 14
+#define GR_DT_XP2 15
+#define GR_DT_XP3 16
+#define GR_DT_GOAL 17
+int gr_diff_config(gr_ctx* ctx, const float* weights, float gamma);
+int64_t gr_diff_row_floats(const gr_ctx* ctx);
+int gr_diff_record(gr_ctx* ctx, const float* actions, float* tape_row, void* stream);
+int gr_diff_loss(gr_ctx* ctx, const float* gates, float* tape_row, float* loss, float* loss_terms, void* stream);
+int gr_diff_backward(gr_ctx* ctx, const float* tape, int32_t steps, float scale, float* grad_actions, void* stream);
 
 #ifdef __cplusplus
 }
